@@ -18,6 +18,9 @@ for every image of the per-GPU batch.  Images are independent, so ranks share no
 Prints ONE JSON line on rank 0 (contract in the task statement) with "roofline" (dominant kernel, HIP-event
 timed, bytes = what the kernel has to move), "cpu_baseline" (+ parity of the GPU's image 0 against it) and
 "other_workloads" (the 4K batch the north_star target is phrased on, and 8192^2).
+
+--dump-outputs DIR writes what the last timed step of the workload computed to DIR/*.npy (dump_outputs); the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -392,10 +395,40 @@ def target_span(wl, res):
             "target": 0.60}
 
 
-def run_workload(wl, steps, warmup, barrier, reduce_max, with_stages, stage_reps, single_leg):
+DUMP_VALUES = 1 << 21       # values of one output that --dump-outputs keeps, summed over the ranks (a larger output is sampled)
+
+
+def dump_positions(numel, k):
+    """the fixed sample --dump-outputs keeps of a flattened output of numel > k values: seeded draws with replacement, deduplicated
+    and sorted (host memory of the order of k)"""
+    return np.unique(np.random.default_rng(0).integers(0, numel, k))
+
+
+def dump_outputs(wl, out_dir, suffix=""):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files (bytes as float32, counts as float64) -- the stego
+    images, the headers and payloads the extractor decoded, its status per image (the payload length it found) and the embed's
+    capacities.  Each rank keeps at most k = DUMP_VALUES // world values of an output: a larger one is flattened and only its values at
+    dump_positions(numel, k) are written, the same positions in every run.  So the files of all ranks together hold at most
+    5 x DUMP_VALUES values (56 MiB) whatever --gpus; the default workload writes about 8.5 MiB at --gpus 1 and 12 MiB at --gpus 8."""
+    torch = wl.torch
+    os.makedirs(out_dir, exist_ok=True)
+    k = DUMP_VALUES // wl.world
+    outs = {"stego": wl.d_stego, "header_out": wl.d_hdr_out, "payload_out": wl.d_pay_out, "status": wl.d_status}
+    if wl.stats:
+        outs["usable_bits"] = wl.d_usable
+    for name, t in outs.items():
+        if t.numel() > k:
+            t = t.reshape(-1)[torch.from_numpy(dump_positions(t.numel(), k)).to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a.astype(np.float32 if a.itemsize <= 2 else np.float64))
+
+
+def run_workload(wl, steps, warmup, barrier, reduce_max, with_stages, stage_reps, single_leg, dump_dir=None):
     for _ in range(warmup):
         wl.step()
     dt = reduce_max(timed(wl.step, steps, barrier))
+    if dump_dir:                # before the embed-only leg and the correctness read overwrite the step's outputs
+        dump_outputs(wl, dump_dir, "_rank%d" % wl.rank if wl.world > 1 else "")
     dte = reduce_max(timed(wl.embed, steps, barrier))
     wl.ctx.sync()
     pix = wl.n_img * wl.W * wl.H
@@ -446,6 +479,8 @@ def main():
     ap.add_argument("--batched-only", action="store_true",
                     help="profiling runs: only the timed steps and the per-stage launches, so that every traced launch is a batched one")
     ap.add_argument("--stage-reps", type=int, default=20)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the workload computed to DIR/<name>.npy (seeded inputs: equal from run to run)")
     args = ap.parse_args()
 
     import torch
@@ -494,7 +529,7 @@ def main():
     wl = Workload(args.workload, torch, S, dev, local, rank, world, args.images, args.slots, not args.no_stats, dist, backend, coll_dev)
     # every rank runs the same legs (timed steps, embed-only, correctness read); rank 0 alone adds the per-stage launches
     res = run_workload(wl, args.steps, args.warmup, barrier, reduce_max, with_stages=(rank == 0), stage_reps=args.stage_reps,
-                       single_leg=(rank == 0 and not args.batched_only))
+                       single_leg=(rank == 0 and not args.batched_only), dump_dir=args.dump_outputs)
     chk = res["check"]
     if world > 1:
         acc = torch.tensor([float(chk["wrong_bits"]), float(chk["bits"]), float(chk["headers_decoded"]), float(chk["payloads_recovered"]),

@@ -20,14 +20,5 @@ def orc():
 
 
 @pytest.fixture(scope="session")
-def ref():
-    """The reference TU compiled in place (oracle/_ref); absent => skip."""
-    from _checkers import Checker, have_ref
-    if not have_ref():
-        pytest.skip("oracle/_ref/libtfref.so not built (needs /root/reference)")
-    return Checker("ref")
-
-
-@pytest.fixture(scope="session")
 def golden_dir():
     return os.path.join(ROOT, "tests", "golden")

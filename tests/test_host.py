@@ -14,7 +14,8 @@ import zlib
 import numpy as np
 import pytest
 
-from _checkers import bins_digest
+import ref_outputs
+from _checkers import REF_CLI, Checker, bins_digest, have_ref
 from steganosaurus_amd import binding as B
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -264,13 +265,18 @@ def test_png_roundtrip_and_variants(host, tmp_path, golden_dir):
     assert host.tfh_image_read(b"/nonexistent.png", None, C.c_uint64(0), C.byref(w), C.byref(h)) == -1
 
 
-def test_png_matches_reference_decoder(host, ref, golden_dir, tmp_path):
+def test_png_matches_reference_decoder(host, golden_dir, tmp_path):
+    want = ref_outputs.recorded()["png"]
     p = os.path.join(golden_dir, "cli_256_hello.png")
-    assert np.array_equal(_read(host, p), ref.png_read(p))
-    img = np.random.default_rng(5).integers(0, 256, (37, 41, 3), dtype=np.uint8)
+    assert ref_outputs.digest(_read(host, p)) == want["cli_256_hello"]
+    img = ref_outputs.png_test_image()
     q = str(tmp_path / "mine.png")
     assert host.tfh_png_write(q.encode(), img.ctypes.data_as(C.c_void_p), 41, 37) == 0
-    assert np.array_equal(ref.png_read(q), img)          # stb reads what we write
+    assert ref_outputs.png_content(q) == want["written_37x41"]       # stb read this content back as `img`
+    if have_ref():
+        ref = Checker("ref")
+        assert np.array_equal(_read(host, p), ref.png_read(p))
+        assert np.array_equal(ref.png_read(q), img)
 
 
 # ------------------------------------------------------------------ CLI without a GPU
@@ -357,22 +363,12 @@ def test_shard_covers_everything():
 
 def test_wrapped_key_from_reference_cli_unwraps(host, tmp_path):
     """The reference's gen-key wraps with its library AEAD, whose Poly1305 tag assembly has the same
-    non-standard carry handling as the in-TU copy: only the compatible variant opens it."""
-    from _checkers import REF_CLI
-    if not os.path.exists(REF_CLI):
-        pytest.skip("reference CLI not built")
-    import base64
-    kf = tmp_path / "w.txt"
-    r = subprocess.run([REF_CLI, "gen-key", "--key-out", str(kf), "--wrap-pass", "pw", "--pbkdf2_iter", "1000"],
-                       capture_output=True, text=True, check=True)
-    key = base64.b64decode(re.search(r"Base64: (\S+)", r.stdout).group(1))
-    blob = base64.b64decode(kf.read_text().strip())
-    assert len(blob) == 80 and blob[:4] == b"TFKW"
-    derived = hashlib.pbkdf2_hmac("sha256", b"pw", blob[4:20], 1000, 44)
-    out = C.create_string_buffer(32)
-    assert host.tfh_aead_open_turtle(derived[:32], blob[20:32], None, C.c_size_t(0), blob[32:64], C.c_size_t(32), blob[64:80], out) == 1
-    assert out.raw == key
-    assert host.tfh_aead_open(derived[:32], blob[20:32], None, C.c_size_t(0), blob[32:64], C.c_size_t(32), blob[64:80], out) == 0
+    non-standard carry handling as the in-TU copy: only the compatible variant opens it (a recorded key
+    file, and a fresh one where the reference CLI is built)."""
+    rec = ref_outputs.recorded()["gen_key"]
+    ref_outputs.unwraps(host, rec["key_b64"], rec["wrapped"])
+    if os.path.exists(REF_CLI):
+        ref_outputs.unwraps(host, *ref_outputs.reference_gen_key(str(tmp_path)))
 
 
 def test_capacity_threshold_transform_matches_reference_compare():
