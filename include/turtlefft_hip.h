@@ -291,6 +291,18 @@ int tfft_bins_sort(tfft_bin* bins, uint32_t* bit_index, uint64_t n);
 int tfft_bins_register_dev(tfft_ctx* ctx, const void* bins_dev, uint64_t n);
 int tfft_set_bit_index(tfft_ctx* ctx, const uint32_t* bit_index, uint64_t n);
 
+/* Phase options of the BATCHED calls (tfft_*_batch[_dev], tfft_*_stream_batch[_dev], tfp_*), the --jitter and --adaptive_alpha of
+ * the reference CLI (S:690-694, S:704-710, S:719):
+ *   jitter: n floats in STREAM order (tfft_walk_jitter, computed before tfft_bins_sort), copied to the device, or NULL.  Every image
+ *           of a batch shares it, as it shares the bin list.  Calls with another n_bits / n_bins fail with TFFT_E_STATE while a jitter
+ *           array is set.
+ *   adaptive_alpha: a = alpha*clamp(|F|/med,0.5,2) with each image's own medians (the fp32 order statistic of the batch path, computed
+ *           on the device whether or not usable_out is given).  Extraction needs no medians when |alpha| < pi/2 (the bit is then the
+ *           side of the line through j and j+pi); with |alpha| >= pi/2 the batched extraction calls return
+ *           TFFT_E_INVALID -- tfft_read_bins[_dev] with the image's medians covers that case.
+ * (ctx, NULL, 0, 0) clears both.  Synchronises with the context's streams.  The single-image calls keep their own arguments. */
+int tfft_set_phase_options(tfft_ctx* ctx, const float* jitter, uint64_t n, int adaptive_alpha);
+
 /* ------------------------------------------------------------ measurement
  * Device-side timing of whatever was enqueued between the two calls on the
  * context's stream (hipEvent pair on that stream). */

@@ -72,6 +72,7 @@ SYMBOLS = {
     "tfft_bins_sort": (_i, [_vp, _vp, _u64]),
     "tfft_set_bit_index": (_i, [_vp, _vp, _u64]),
     "tfft_bins_register_dev": (_i, [_vp, _vp, _u64]),
+    "tfft_set_phase_options": (_i, [_vp, _vp, _u64, _i]),
     "tfft_profile_stage": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _u64, _d, C.POINTER(C.c_float), _pi]),
     "tfft_timer_begin": (_i, [_vp]),
     "tfft_timer_end": (_i, [_vp, C.POINTER(C.c_float)]),
@@ -214,6 +215,15 @@ class Context:
             return
         idx = np.ascontiguousarray(bit_index, np.uint32)
         _check(self.lib.tfft_set_bit_index(self.h, _ptr(idx), len(idx)), "tfft_set_bit_index")
+
+    def set_phase_options(self, jitter=None, adaptive=False):
+        """Jitter (stream order, one float per bin of the list; None: none) and adaptive alpha of the later BATCHED calls;
+        set_phase_options() clears both."""
+        if jitter is None:
+            _check(self.lib.tfft_set_phase_options(self.h, None, 0, int(adaptive)), "tfft_set_phase_options")
+            return
+        jit = np.ascontiguousarray(jitter, np.float32)
+        _check(self.lib.tfft_set_phase_options(self.h, _ptr(jit), len(jit), int(adaptive)), "tfft_set_phase_options")
 
     def bins_register_dev(self, bins_ptr, n):
         _check(self.lib.tfft_bins_register_dev(self.h, _ptr(bins_ptr), n), "tfft_bins_register_dev")

@@ -80,7 +80,9 @@ struct tfft_ctx {
                          unsigned* cnt = nullptr; unsigned* off = nullptr; TileBin* ent = nullptr; uint64_t cap = 0; int nb_cap = 0;
                          // what the buckets / the last-row scalar currently describe (tfft_bins_register_dev: reused while the registered list is the one passed in)
                          const void* built_for = nullptr; uint64_t built_n = 0; int built_ph = 0, built_pw = 0, built_g = 0; const void* built_index = nullptr; bool built_bad = false;
-                         const void* row_for = nullptr; uint64_t row_n = 0; int row_ph = 0, row_pw = 0; } tb[2];
+                         const void* row_for = nullptr; uint64_t row_n = 0; int row_ph = 0, row_pw = 0;
+                         float2* jp = nullptr; uint64_t jp_cap = 0; uint64_t jp_for = 0;      /* the phase options' jitter in bucket order (ColParams::em_jp), gathered for ph_version jp_for */
+                       } tb[2];
     const void* reg_bins = nullptr; uint64_t reg_n = 0;      // tfft_bins_register_dev
     int embed_delta = 1;                  // batched embeds: stego = cover + IFFT(F' - F) (TFFT_EMBED_DELTA=0: write F' into the spectrum and invert it)
     int tile_read = 1;                    // TFFT_TILE_READ=0: row-limited spectrum + k_read always; 1: tile read for chunks of >= 8 images; 3: always; 2: always, with the global-atomic bucket build
@@ -96,6 +98,12 @@ struct tfft_ctx {
     int n_cus = 0, collect_resident = 0;  // grid sizing of the full median pass: fill every CU to the same depth
     uint32_t* bit_index = nullptr;        // tfft_set_bit_index: bins[i] carries stream bit bit_index[i]
     uint64_t bit_index_n = 0;
+    // tfft_set_phase_options: the batched calls' jitter (device, stream order, ph_n floats; nullptr = none) and adaptive alpha.
+    // ph_version changes with every call of the setter (0: never set), so that bucket-order copies and cached sequences can tell
+    float* ph_jit = nullptr;
+    uint64_t ph_n = 0;
+    int ph_adaptive = 0;
+    uint64_t ph_version = 0;
     std::map<int, float2*> tw;            // N -> table exp(+2 pi i j/N), j < N
     std::map<std::tuple<int, int, int, int>, float2*> dc;   // (valid, N, center, kind) -> DC-removal table, see get_dc_table
     float dc_bias = 128.0f;               // constant taken out of the pixels before the forward transform and put back analytically (see
@@ -216,9 +224,10 @@ enum Stage { ROWS_FWD = 0, COLS_FWD_A = 1, COLS_FWD_B = 2, EMBED = 3, COLS_INV_A
 int get_dc_table(tfft_ctx* c, int valid, int N, int center, int kind, double scale, const float2** out);
 void invalidate_graphs(tfft_ctx* c);      // cached launch sequences hold raw device pointers: dropped whenever a buffer is reallocated
 
-static void copy_embed_fields(ColParams& cp, const ColParams& e) {
+static void copy_embed_fields(ColParams& cp, const ColParams& e, bool inverse) {
     cp.rd_bins = e.rd_bins; cp.rd_off = e.rd_off; cp.trash = e.trash;
     cp.em_n = e.em_n; cp.em_cos = e.em_cos; cp.em_sin = e.em_sin; cp.em_fl = e.em_fl; cp.em_pb = e.em_pb; cp.em_on = 1; cp.em_m2 = e.em_m2;
+    if (inverse) { cp.em_jp = e.em_jp; cp.em_med = e.em_med; cp.em_alpha = e.em_alpha; }      // (the phase options belong to COLS_EMBED)
     cp.st_sel = e.st_sel; cp.st_cand = e.st_cand; cp.st_cand_stride = e.st_cand_stride; cp.st_partial = e.st_partial; cp.st_amb = e.st_amb;
     cp.st_col0 = e.st_col0; cp.st_slo = e.st_slo; cp.st_shi = e.st_shi; cp.st_cap = e.st_cap; cp.st_PW = e.st_PW;
 }
@@ -273,8 +282,8 @@ int enqueue_fft_stage(tfft_ctx* c, int s0, int n, int stage, const uint8_t* rgb_
                 rc = get_dc_table(c, s.H, s.PH, s.center, 0, (double)c->dc_bias, &cp.dc_ah); if (rc) return rc;
                 rc = get_dc_table(c, s.W, s.PWi, s.center, 1, 1.0, &cp.dc_aw); if (rc) return rc;
             }
-                if (md.fwd_read) { const ColParams& r = *md.fwd_read; cp.rd_bins = r.rd_bins; cp.rd_off = r.rd_off; cp.rd_bits = r.rd_bits; cp.rd_n = r.rd_n; cp.trash = c->trash; cp.tiles_per_block = c->cols_tiles_read; }
-                else if (md.fwd_emit) { copy_embed_fields(cp, *md.fwd_emit); if (!c->cols_tiles_forced && pl.log_n2 <= 8) cp.tiles_per_block = 2; if (cp.st_sel && c->cols_tiles_stat) cp.tiles_per_block = c->cols_tiles_stat; }
+                if (md.fwd_read) { const ColParams& r = *md.fwd_read; cp.rd_bins = r.rd_bins; cp.rd_off = r.rd_off; cp.rd_bits = r.rd_bits; cp.rd_n = r.rd_n; cp.em_jp = r.em_jp; cp.trash = c->trash; cp.tiles_per_block = c->cols_tiles_read; }
+                else if (md.fwd_emit) { copy_embed_fields(cp, *md.fwd_emit, false); if (!c->cols_tiles_forced && pl.log_n2 <= 8) cp.tiles_per_block = 2; if (cp.st_sel && c->cols_tiles_stat) cp.tiles_per_block = c->cols_tiles_stat; }
                 else if (md.fwd_plain_extra) copy_plain_extra(cp, *md.fwd_plain_extra);
                 HIPCHK(c, launch_cols(tmp, md.fwd_out_override ? md.fwd_out_override : spec, tw_h, cp, pl.log_n2, +1, 3 * n, st));
             } else {   // for every n2: length-N1 FFT over rows n1*N2+n2, times w^(n2*k1), in place
@@ -291,15 +300,15 @@ int enqueue_fft_stage(tfft_ctx* c, int s0, int n, int stage, const uint8_t* rgb_
                 rc = get_dc_table(c, s.H, s.PH, s.center, 0, (double)c->dc_bias, &cp.dc_ah); if (rc) return rc;
                 rc = get_dc_table(c, s.W, s.PWi, s.center, 1, 1.0, &cp.dc_aw); if (rc) return rc;
             }
-            if (md.fwd_read) { const ColParams& r = *md.fwd_read; cp.rd_bins = r.rd_bins; cp.rd_off = r.rd_off; cp.rd_bits = r.rd_bits; cp.rd_n = r.rd_n; cp.trash = c->trash; cp.tiles_per_block = c->cols_tiles_read; }
-            else if (md.fwd_emit) { copy_embed_fields(cp, *md.fwd_emit); if (!c->cols_tiles_forced && pl.log_n2 <= 8) cp.tiles_per_block = 2; if (cp.st_sel && c->cols_tiles_stat) cp.tiles_per_block = c->cols_tiles_stat; }
+            if (md.fwd_read) { const ColParams& r = *md.fwd_read; cp.rd_bins = r.rd_bins; cp.rd_off = r.rd_off; cp.rd_bits = r.rd_bits; cp.rd_n = r.rd_n; cp.em_jp = r.em_jp; cp.trash = c->trash; cp.tiles_per_block = c->cols_tiles_read; }
+            else if (md.fwd_emit) { copy_embed_fields(cp, *md.fwd_emit, false); if (!c->cols_tiles_forced && pl.log_n2 <= 8) cp.tiles_per_block = 2; if (cp.st_sel && c->cols_tiles_stat) cp.tiles_per_block = c->cols_tiles_stat; }
                 else if (md.fwd_plain_extra) copy_plain_extra(cp, *md.fwd_plain_extra);
             HIPCHK(c, launch_cols(tmp, md.fwd_out_override ? md.fwd_out_override : spec, tw_h, cp, pl.log_n2, +1, 3 * n, st));
             return TFFT_OK;
         case COLS_INV_A:
             if (pl.direct) {
                 cp.G = 1; cp.in_a = 1; cp.in_b = 0; cp.out_a = 1; cp.out_b = 0; cp.in_rows = s.PH; cp.out_rows = s.H; cp.tw_out = 0;
-                if (md.inv_embed) { copy_embed_fields(cp, *md.inv_embed); cp.tiles_per_block = c->cols_tiles_embed ? c->cols_tiles_embed : (pl.log_n2 >= 9 ? 2 : 16); }
+                if (md.inv_embed) { copy_embed_fields(cp, *md.inv_embed, true); cp.tiles_per_block = c->cols_tiles_embed ? c->cols_tiles_embed : (pl.log_n2 >= 9 ? 2 : 16); }
                 else if (c->dc_bias != 0.0f) {
                     rc = get_dc_table(c, s.H, s.PH, s.center, 0, (double)c->dc_bias, &cp.dc_ah); if (rc) return rc;
                     rc = get_dc_table(c, s.W, s.PWi, s.center, 1, 1.0, &cp.dc_aw); if (rc) return rc;
@@ -307,7 +316,7 @@ int enqueue_fft_stage(tfft_ctx* c, int s0, int n, int stage, const uint8_t* rgb_
                 HIPCHK(c, launch_cols(spec, md.inv_via_spec ? spec : tmp, tw_h, cp, pl.log_n2, -1, 3 * n, st));
             } else {   // for every k1: length-N2 inverse over rows k1+N1*k2 -> rows k1*N2+n2, times w^-(n2*k1)
                 cp.G = N1; cp.in_a = N1; cp.in_b = 1; cp.out_a = 1; cp.out_b = N2; cp.in_rows = s.PH; cp.out_rows = s.PH; cp.tw_out = 1;
-                if (md.inv_embed) { copy_embed_fields(cp, *md.inv_embed); cp.tiles_per_block = c->cols_tiles_embed ? c->cols_tiles_embed : (pl.log_n2 >= 9 ? 2 : 16); }
+                if (md.inv_embed) { copy_embed_fields(cp, *md.inv_embed, true); cp.tiles_per_block = c->cols_tiles_embed ? c->cols_tiles_embed : (pl.log_n2 >= 9 ? 2 : 16); }
                 else if (c->dc_bias != 0.0f) {
                     rc = get_dc_table(c, s.H, s.PH, s.center, 0, (double)c->dc_bias, &cp.dc_ah); if (rc) return rc;
                     rc = get_dc_table(c, s.W, s.PWi, s.center, 1, 1.0, &cp.dc_aw); if (rc) return rc;
@@ -406,6 +415,12 @@ EmbedParams embed_params(const tfft_ctx* c, const Slot& s, uint64_t n, double al
 }
 // a bit index, once set, must describe exactly the bin list it is used with
 static inline bool index_ok(const tfft_ctx* c, uint64_t n) { return !c->bit_index || c->bit_index_n == n; }
+// ... and so must the jitter of the phase options (batched calls only)
+static inline bool phase_ok(const tfft_ctx* c, uint64_t n) { return !c->ph_jit || c->ph_n == n; }
+// what a cached launch sequence of a batched call depends on besides its arguments
+static void phase_key(const tfft_ctx* c, std::vector<uint64_t>& key) {
+    key.push_back((uint64_t)(uintptr_t)c->ph_jit); key.push_back(c->ph_n); key.push_back((uint64_t)c->ph_adaptive); key.push_back(c->ph_version);
+}
 
 CapParams cap_params(const tfft_ctx* c, const Slot& s, double rmin, double rmax) {
     CapParams p{};
@@ -638,8 +653,8 @@ int tfft_destroy(tfft_ctx* c) {
     invalidate_graphs(c);
     (void)hipFree(c->img_pool); (void)hipFree(c->spec_pool); (void)hipFree(c->tmp_pool); (void)hipFree(c->cand_pool);
     (void)hipFree(c->col0_pool);
-    (void)hipFree(c->sel); (void)hipFree(c->med); (void)hipFree(c->partial); (void)hipFree(c->amb); (void)hipFree(c->usable); (void)hipFree(c->err); (void)hipFree(c->ex_cand); (void)hipFree(c->ex_val); (void)hipFree(c->ex_below); (void)hipFree(c->ex_n); for (auto& kv : c->ex_table) (void)hipFree(kv.second); (void)hipFree(c->trash); (void)hipFree(c->bit_index); (void)hipFree(c->last_row);
-    for (auto& b : c->tb) { (void)hipFree(b.cnt); (void)hipFree(b.off); (void)hipFree(b.ent); (void)hipFree(b.fl); (void)hipFree(b.pb); }
+    (void)hipFree(c->sel); (void)hipFree(c->med); (void)hipFree(c->partial); (void)hipFree(c->amb); (void)hipFree(c->usable); (void)hipFree(c->err); (void)hipFree(c->ex_cand); (void)hipFree(c->ex_val); (void)hipFree(c->ex_below); (void)hipFree(c->ex_n); for (auto& kv : c->ex_table) (void)hipFree(kv.second); (void)hipFree(c->trash); (void)hipFree(c->bit_index); (void)hipFree(c->last_row); (void)hipFree(c->ph_jit);
+    for (auto& b : c->tb) { (void)hipFree(b.cnt); (void)hipFree(b.off); (void)hipFree(b.ent); (void)hipFree(b.fl); (void)hipFree(b.pb); (void)hipFree(b.jp); }
     for (auto& kv : c->tw) (void)hipFree(kv.second);
     for (auto& kv : c->dc) (void)hipFree(kv.second);
     (void)hipFree(c->stage_bins); (void)hipFree(c->stage_bits); (void)hipFree(c->stage_jit); (void)hipFree(c->stage_out);
@@ -955,6 +970,31 @@ int tfft_set_bit_index(tfft_ctx* c, const uint32_t* bit_index, uint64_t n) {
     return TFFT_OK;
 }
 
+int tfft_set_phase_options(tfft_ctx* c, const float* jitter, uint64_t n, int adaptive_alpha) {
+    if (!c || (jitter && n == 0)) return TFFT_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    // calls enqueued before may still read the old array: it goes only once they are done
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
+    invalidate_graphs(c);
+    c->ph_version++;
+    c->ph_adaptive = adaptive_alpha ? 1 : 0;
+    if (!jitter) {
+        (void)hipFree(c->ph_jit);
+        c->ph_jit = nullptr; c->ph_n = 0;
+        return TFFT_OK;
+    }
+    if (c->ph_n != n || !c->ph_jit) {
+        (void)hipFree(c->ph_jit);
+        c->ph_jit = nullptr; c->ph_n = 0;
+        int rc = dev_alloc(c, (void**)&c->ph_jit, n * sizeof(float));
+        if (rc) return rc;
+    }
+    HIPCHK(c, hipMemcpy(c->ph_jit, jitter, n * sizeof(float), hipMemcpyHostToDevice));
+    c->ph_n = n;
+    return TFFT_OK;
+}
+
 int tfft_embed_bins_dev(tfft_ctx* c, int slot, const void* bins, const void* bits, const void* jitter, uint64_t n,
                         double alpha, int adaptive, const double med[3]) {
     if (!slot_ok(c, slot) || (n && (!bins || !bits)) || (adaptive && !med)) return TFFT_E_INVALID;
@@ -1092,6 +1132,7 @@ static int build_buckets(tfft_ctx* c, int which, const tfft_bin* bins, uint64_t 
         HIPCHK(c, launch_bucket_bins(bins, c->bit_index, n_bits, s.PH, s.PWi, G, tb.cnt, tb.off, tb.ent, c->err, c->tile_read == 2, st));
         tb.built_for = registered ? bins : nullptr; tb.built_n = n_bits; tb.built_ph = s.PH; tb.built_pw = s.PWi; tb.built_g = G; tb.built_index = c->bit_index;
         tb.built_bad = false;
+        tb.jp_for = 0;
         if (registered && st == c->stream) {      // the cached buckets outlive this call: so does the verdict on the list (one sync per registration and geometry)
             const int rc = check_err_flag(c);
             if (rc == TFFT_E_BIN_RANGE) tb.built_bad = true;
@@ -1101,6 +1142,27 @@ static int build_buckets(tfft_ctx* c, int which, const tfft_bin* bins, uint64_t 
     // every call on a registered list with bins outside the grid reports them (at its end, as the call that built the buckets does),
     // not only the first: the flag the builder raised is raised again
     if (tb.built_bad) HIPCHK(c, hipMemsetAsync(c->err, 0x01, sizeof(int), st));
+    return TFFT_OK;
+}
+
+// the phase options' jitter in the order of the buckets just built (once per bucket build and setting: a registered list keeps it)
+static int gather_jitter(tfft_ctx* c, int which, uint64_t n_bits, int nb, hipStream_t st) {
+    auto& tb = c->tb[which];
+    if (!c->ph_jit) return TFFT_OK;
+    if (n_bits > tb.jp_cap || !tb.jp) {
+        (void)hipStreamSynchronize(c->stream);
+        if (c->stream2) (void)hipStreamSynchronize(c->stream2);
+        invalidate_graphs(c);
+        (void)hipFree(tb.jp); tb.jp = nullptr; tb.jp_cap = 0; tb.jp_for = 0;
+        const uint64_t cap = n_bits + n_bits / 4 + 1024;
+        if (dev_alloc(c, (void**)&tb.jp, cap * sizeof(float2))) return TFFT_E_NOMEM;
+        tb.jp_cap = cap;
+    }
+    if (tb.jp_for != c->ph_version) {
+        if (tb.jp_for) c->graphs_stale = true;      // (as for the buckets: a captured sequence without this gather must not be replayed)
+        HIPCHK(c, launch_gather_jitter(tb.ent, tb.off + nb, c->ph_jit, n_bits, tb.jp, st));
+        tb.jp_for = c->ph_version;
+    }
     return TFFT_OK;
 }
 
@@ -1224,6 +1286,9 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
 static int embed_chunk(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, const tfft_bin* bins, const uint8_t* bits,
                        uint64_t n_bits, double alpha, double rmin, double rmax, double magmin,
                        unsigned long long* usable, uint8_t* rgb_out, hipStream_t st, uint64_t limit = ~0ull, const FrameSrc* frame = nullptr) {
+    // adaptive alpha needs every image's medians before the embed: the statistics run whether or not the caller asked for the
+    // capacities (these then land in the context's own buffer)
+    if (!usable && c->ph_adaptive && n_bits > 0) usable = c->usable + s0;
     int rc = usable ? stats_clean_if_dirty(c, st) : TFFT_OK;
     if (!rc) rc = embed_chunk_impl(c, s0, g, rgb_in, bins, bits, n_bits, alpha, rmin, rmax, magmin, usable, rgb_out, st, limit, frame);
     if (!rc && usable && c->stats_fail_once) {      // test hook (TFFT_STATS_FAIL_ONCE): as if the sequence had broken off -- garbage in the select state, an error out
@@ -1238,8 +1303,10 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
                             uint64_t n_bits, double alpha, double rmin, double rmax, double magmin,
                             unsigned long long* usable, uint8_t* rgb_out, hipStream_t st, uint64_t limit, const FrameSrc* frame) {
     const Slot& s = c->slots[s0];
-    if (!index_ok(c, n_bits)) return TFFT_E_STATE;
-    EmbedParams ep = embed_params(c, s, n_bits, alpha, 0, nullptr, false);
+    if (!index_ok(c, n_bits) || !phase_ok(c, n_bits)) return TFFT_E_STATE;
+    const bool adaptive = c->ph_adaptive != 0;
+    EmbedParams ep = embed_params(c, s, n_bits, alpha, adaptive, nullptr, c->ph_jit != nullptr);
+    if (adaptive) ep.med_dev = c->med + 3 * s0;      // (the statistics below run before the embed: see `async`)
     if (limit < n_bits) ep.limit = limit;      // the stream is shorter than the bin list (image i's bits still n_bits apart)
     if (frame) { ep.frame_hdr = frame->hdr; ep.frame_pay = frame->pay; ep.frame_plen = frame->plen; }
     // Delta embedding.  The inverse transform is linear and IFFT(F) is the cover itself, so the stego image is cover + IFFT(F' - F),
@@ -1247,7 +1314,8 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
     // forward column step, which has every tile in LDS, writes the values of the listed bins out in bucket order; the first inverse
     // column step builds its tiles from that list instead of reading the spectrum; nothing writes F' anywhere, and the row kernel adds
     // its result to the cover's pixels.  (The bucket build is per call unless the list is registered, tfft_bins_register_dev.)
-    const bool delta = c->embed_delta && !ep.generic && n_bits > 0;      // whatever the chunk size: the bytes of a stego image do not depend on how the batch was cut
+    // (jitter and adaptive alpha ride along: the entries carry the jitter phasor and the image's medians scale alpha)
+    const bool delta = c->embed_delta && alpha > 0.0 && alpha < M_PI && n_bits > 0;      // whatever the chunk size: the bytes of a stego image do not depend on how the batch was cut
     const int which = (c->stream2 && st == c->stream2) ? 1 : 0;
     ColParams em{};
     int rc;
@@ -1261,6 +1329,10 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
         auto& tb = c->tb[which];
         em.rd_bins = tb.ent; em.rd_off = tb.off; em.trash = c->trash; em.em_fl = tb.fl + (size_t)s0 * n_bits; em.em_pb = tb.pb + (size_t)s0 * n_bits;
         em.em_n = n_bits; em.em_cos = ep.cos_a; em.em_sin = ep.sin_a;
+        rc = gather_jitter(c, which, n_bits, nb, st);
+        if (rc) return rc;
+        em.em_jp = c->ph_jit ? tb.jp : nullptr;
+        em.em_med = adaptive ? c->med + 3 * s0 : nullptr; em.em_alpha = (float)alpha;
         if (usable) {
             CapParams p0 = cap_params(c, s, rmin, rmax);
             if (stats_m2_applies(c, s, p0)) { em.em_m2 = 1; em.st_col0 = c->col0_pool + (size_t)s0 * 3 * s.PH; }
@@ -1282,7 +1354,7 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
             if (rc) return rc;
             // the select chain is five small dependent launches: on a side stream beside the inverse transform, which does not wait for it
             hipStream_t sst = st;
-            if (c->stats_async) {
+            if (c->stats_async && !adaptive) {
                 if (!c->stream_stats[which]) {
                     HIPCHK(c, create_stats_stream(c, &c->stream_stats[which]));
                     HIPCHK(c, hipEventCreateWithFlags(&c->ev_stats_fork[which], hipEventDisableTiming));
@@ -1294,6 +1366,10 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
             }
             rc = enqueue_tilestats_select(c, s0, g, sst);
             if (rc) return rc;
+            if (adaptive) {         // the embed needs the medians: select, gated re-run and fallbacks all finish before the inverse step
+                rc = enqueue_tilestats_tail(c, s0, g, rgb_in, st, p, usable);
+                if (rc) return rc;
+            }
             StageMode mi;
             mi.inv_embed = &em; mi.inv_cover = rgb_in; mi.inv_via_spec = true;
             rc = enqueue_inverse(c, s0, g, rgb_out, st, mi);
@@ -1302,7 +1378,7 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
                 HIPCHK(c, hipEventRecord(c->ev_stats_join[which], sst));
                 HIPCHK(c, hipStreamWaitEvent(st, c->ev_stats_join[which], 0));
             }
-            return enqueue_tilestats_tail(c, s0, g, rgb_in, st, p, usable);
+            return adaptive ? TFFT_OK : enqueue_tilestats_tail(c, s0, g, rgb_in, st, p, usable);
         }
     }
     StageMode md;
@@ -1310,7 +1386,7 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
     rc = enqueue_forward(c, s0, g, rgb_in, st, md);
     if (rc) return rc;
     hipStream_t sst = st;       // the stream the statistics run on
-    const bool async = delta && usable && c->stats_async;
+    const bool async = delta && usable && c->stats_async && !adaptive;      // (adaptive: the embed waits for the medians)
     if (async) {
         if (!c->stream_stats[which]) {
             HIPCHK(c, create_stats_stream(c, &c->stream_stats[which]));
@@ -1343,22 +1419,26 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
         }
         return rc;
     }
-    HIPCHK(c, launch_embed(c->spec(s0), bins, bits, nullptr, ep, g, c->err, st));
+    HIPCHK(c, launch_embed(c->spec(s0), bins, bits, c->ph_jit, ep, g, c->err, st));
     return enqueue_inverse(c, s0, g, rgb_out, st);
 }
 static int extract_chunk(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, const tfft_bin* bins, uint64_t n_bits,
                          double alpha, uint8_t* bits_out, hipStream_t st) {
     const Slot& s = c->slots[s0];
-    if (!index_ok(c, n_bits)) return TFFT_E_STATE;
+    if (!index_ok(c, n_bits) || !phase_ok(c, n_bits)) return TFFT_E_STATE;
+    // adaptive alpha with |alpha| < pi/2: a = alpha*clamp(.., 0.5, 2) keeps the sign of alpha and |a| < pi, so the targets j +- a are
+    // symmetric about j and j + pi and the bit is the side of that line -- what the fixed-alpha read decides.
+    // Beyond, the decision depends on the medians: the single-image calls cover that case
+    if (c->ph_adaptive && !(fabs(alpha) < M_PI / 2)) return TFFT_E_INVALID;
     const int which = (c->stream2 && st == c->stream2) ? 1 : 0;
-    EmbedParams ep = embed_params(c, s, n_bits, alpha, 0, nullptr, false);
+    EmbedParams ep = embed_params(c, s, n_bits, alpha, 0, nullptr, c->ph_jit != nullptr);
     int rc;
     // (the bucket build is per call: it pays off from about 8 images per chunk; TFFT_TILE_READ=2/3 force it)
     // a registered list keeps its buckets (no per-call build to pay for): then the tile-resident read also serves small chunks of LARGE
     // images (one 4K image: 0.739 -> 0.725 ms per round trip; one 1080p image has too few tiles to fill the chip: 0.265 -> 0.301)
     const bool reg_large = bins == c->reg_bins && n_bits == c->reg_n && (unsigned long long)s.PH * s.PWi >= (1ull << 23);
     // (an alpha outside (0, pi) takes the general phase comparison of k_read: the tile kernel reads the sign of Im only)
-    if (c->tile_read && n_bits > 0 && !ep.generic && (g >= 8 || c->tile_read >= 2 || reg_large)) {
+    if (c->tile_read && n_bits > 0 && alpha > 0.0 && alpha < M_PI && (g >= 8 || c->tile_read >= 2 || reg_large)) {
         // The spectrum is only ever read at the bins of the list: bucket them by column tile and let the final
         // forward column step read the bits out of its LDS-resident tiles -- no spectrum store, no k_read.
         const ColPlan pl = plan_cols(c, s.PH, s.PWi, g);
@@ -1369,8 +1449,11 @@ static int extract_chunk(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, cons
         HIPCHK(c, hipMemsetAsync(bits_out, 0, (size_t)g * n_bits, st));          // bins the walk would never produce read as 0 (k_read does the same)
         rc = build_buckets(c, which, bins, n_bits, s, G, st);
         if (rc) return rc;
+        rc = gather_jitter(c, which, n_bits, nb, st);
+        if (rc) return rc;
         ColParams rd{};
         rd.rd_bins = tb.ent; rd.rd_off = tb.off; rd.rd_bits = bits_out; rd.rd_n = n_bits; rd.trash = c->trash;
+        rd.em_jp = c->ph_jit ? tb.jp : nullptr;
         StageMode md;
         md.fwd_read = &rd;
         rc = enqueue_forward(c, s0, g, rgb_in, st, md);
@@ -1388,7 +1471,7 @@ static int extract_chunk(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, cons
         md.fwd_last_row = last_row;
         rc = enqueue_forward(c, s0, g, rgb_in, st, md);
         if (rc) return rc;
-        HIPCHK(c, launch_read(c->spec(s0), bins, nullptr, ep, g, bits_out, c->err, st));
+        HIPCHK(c, launch_read(c->spec(s0), bins, c->ph_jit, ep, g, bits_out, c->err, st));
     }
     for (int i = 0; i < g; i++) c->slots[s0 + i].has_spec = false;      // partial or no spectrum: not for tfft_medians & co
     return TFFT_OK;
@@ -1453,10 +1536,11 @@ int tfft_embed_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, 
                          const void* bits_dev, uint64_t n_bits, double alpha, double rmin, double rmax, double magmin,
                          void* usable_out_dev, void* rgb_out_dev) {
     if (!c || n_images < 0 || !rgb_dev || !rgb_out_dev || (n_bits && (!bins_dev || !bits_dev))) return TFFT_E_INVALID;
-    if (!index_ok(c, n_bits)) return TFFT_E_STATE;
-    const std::vector<uint64_t> key = {1, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), key_bits(bits_dev),
+    if (!index_ok(c, n_bits) || !phase_ok(c, n_bits)) return TFFT_E_STATE;
+    std::vector<uint64_t> key = {1, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), key_bits(bits_dev),
                                        n_bits, key_bits(alpha), key_bits(rmin), key_bits(rmax), key_bits(magmin), key_bits(usable_out_dev),
                                        key_bits(rgb_out_dev), key_bits(c->bit_index), key_bits((double)c->dc_bias)};
+    phase_key(c, key);
     return with_graph(c, n_images, key,
                       [&] { return embed_batch_dev_impl(c, n_images, rgb_dev, w, h, center, bins_dev, bits_dev, n_bits, alpha, rmin, rmax, magmin, usable_out_dev, rgb_out_dev); },
                       [&] { return batch_after(c, n_images, w, h, center); });
@@ -1489,9 +1573,11 @@ static bool read_is_simple(double alpha) { return alpha > 0.0 && alpha < M_PI; }
 int tfft_extract_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, const void* bins_dev,
                            uint64_t n_bits, double alpha, void* bits_out_dev) {
     if (!c || n_images < 0 || !rgb_dev || (n_bits && (!bins_dev || !bits_out_dev))) return TFFT_E_INVALID;
-    if (!index_ok(c, n_bits)) return TFFT_E_STATE;
-    const std::vector<uint64_t> key = {2, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), n_bits,
+    if (!index_ok(c, n_bits) || !phase_ok(c, n_bits)) return TFFT_E_STATE;
+    if (c->ph_adaptive && !(fabs(alpha) < M_PI / 2)) return TFFT_E_INVALID;      // (see extract_chunk)
+    std::vector<uint64_t> key = {2, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), n_bits,
                                        key_bits(alpha), key_bits(bits_out_dev), key_bits(c->bit_index), key_bits((double)c->dc_bias)};
+    phase_key(c, key);
     return with_graph(c, read_is_simple(alpha) ? n_images : 0, key,
                       [&] { return extract_batch_dev_impl(c, n_images, rgb_dev, w, h, center, bins_dev, n_bits, alpha, bits_out_dev); },
                       [&] { return batch_after(c, n_images, w, h, center); });
@@ -1538,12 +1624,13 @@ int tfft_embed_stream_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, 
     if (n_bins < 912 || payload_len > (n_bins - 912) / 56) return TFFT_E_INVALID;      // (before the multiplication: a huge length must not wrap)
     const uint64_t n_bits = 38ull * 24 + payload_len * 56;           // S:986-995
     if (n_bits > n_bins) return TFFT_E_INVALID;                      // the caller's walk is shorter than the stream
-    if (!index_ok(c, n_bins)) return TFFT_E_STATE;
+    if (!index_ok(c, n_bins) || !phase_ok(c, n_bins)) return TFFT_E_STATE;
     int rc = ensure_stream(c, n_bins);                                // (may reallocate: before any cached sequence is looked up)
     if (rc) return rc;
-    const std::vector<uint64_t> key = {3, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), n_bins,
+    std::vector<uint64_t> key = {3, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), n_bins,
                                        key_bits(header_dev), key_bits(payload_dev), payload_len, key_bits(alpha), key_bits(rmin), key_bits(rmax),
                                        key_bits(magmin), key_bits(usable_out_dev), key_bits(rgb_out_dev), key_bits(c->bit_index), key_bits((double)c->dc_bias)};
+    phase_key(c, key);
     return with_graph(c, n_images, key,
                       [&] { return embed_stream_batch_dev_impl(c, n_images, rgb_dev, w, h, center, bins_dev, n_bins, header_dev, payload_dev, payload_len, alpha,
                                                                rmin, rmax, magmin, usable_out_dev, rgb_out_dev); },
@@ -1575,13 +1662,15 @@ int tfft_extract_stream_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev
                                   void* status_out_dev, void* raw_bits_out_dev) {
     if (!c || n_images < 0 || !rgb_dev || !bins_dev || n_bins == 0 || !header_out_dev || !status_out_dev || (max_payload_len && !payload_out_dev))
         return TFFT_E_INVALID;
-    if (!index_ok(c, n_bins)) return TFFT_E_STATE;
+    if (!index_ok(c, n_bins) || !phase_ok(c, n_bins)) return TFFT_E_STATE;
+    if (c->ph_adaptive && !(fabs(alpha) < M_PI / 2)) return TFFT_E_INVALID;      // (see extract_chunk)
     int rc = TFFT_OK;
     if (!raw_bits_out_dev) { rc = ensure_stream(c, n_bins); if (rc) return rc; }
     else if (!c->stream_plen && dev_alloc(c, (void**)&c->stream_plen, (size_t)c->n_slots * sizeof(unsigned))) return TFFT_E_NOMEM;
-    const std::vector<uint64_t> key = {4, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), n_bins,
+    std::vector<uint64_t> key = {4, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), n_bins,
                                        key_bits(alpha), key_bits(header_out_dev), key_bits(payload_out_dev), max_payload_len, key_bits(status_out_dev),
                                        key_bits(raw_bits_out_dev), key_bits(c->bit_index), key_bits((double)c->dc_bias)};
+    phase_key(c, key);
     return with_graph(c, read_is_simple(alpha) ? n_images : 0, key,
                       [&] { return extract_stream_batch_dev_impl(c, n_images, rgb_dev, w, h, center, bins_dev, n_bins, alpha, header_out_dev, payload_out_dev,
                                                                  max_payload_len, status_out_dev, raw_bits_out_dev); },

@@ -47,6 +47,10 @@ struct ColParams {
     const uint8_t* em_pb;            // COLS_EMBED: em_n stream bits per image in the same order (k_gather_bits; 2 = not written)
     uint64_t em_n;                   // list stride between images (the length of the bin list)
     float em_cos, em_sin;
+    // phase options of the batched calls (tfft_set_phase_options); COLS_EMBED and COLS_READ only
+    const float2* em_jp;             // jitter as unit phasors (cos j, sin j), indexed like rd_bins (shared by all images); nullptr = no jitter
+    const float* em_med;             // COLS_EMBED, adaptive alpha: 3 medians |F| per image of the launch; nullptr = the fixed em_cos / em_sin
+    float em_alpha;                  // ... and the alpha they scale (S:704-710)
     // statistics inside the last forward step (COLS_STAT = COLS_EMIT without the spectrum store): every value is classified against
     // the bracket of its plane's SelectState exactly as k_collect_bracket does (weight below, candidates, capacity counts, parked
     // values); the packed column 0 goes to st_col0 for k_col0_stats
@@ -93,6 +97,7 @@ struct EmbedParams {
     uint64_t limit;              // embed only: stream bits >= limit are not written (the stream is shorter than the bin list)
     // embed only, stream pipelines: the bits come straight out of the packed frame (38-byte header, frame_plen payload bytes per image)
     const uint8_t* frame_hdr; const uint8_t* frame_pay; uint64_t frame_plen;
+    const float* med_dev;        // adaptive, batched calls: 3 medians per image on the device (image i at med_dev + 3*i) instead of med[]
 };
 
 struct CapParams {
@@ -184,6 +189,8 @@ hipError_t launch_stat_settle(const float2* spec, int PH, int PW, size_t img_str
                               unsigned* partial, float* amb, unsigned long long* usable, hipStream_t s);
 hipError_t launch_gather_bits(const TileBin* ent, const unsigned* n_ent, const uint8_t* bits, const uint8_t* hdr, const uint8_t* pay, uint64_t plen,
                               uint64_t n, uint64_t limit, int n_images, uint8_t* out, hipStream_t s);
+// jitter (stream order) gathered into bucket order as unit phasors: out[e] = (cos, sin)(jitter[ent[e].bit]), e < *n_ent
+hipError_t launch_gather_jitter(const TileBin* ent, const unsigned* n_ent, const float* jitter, uint64_t n, float2* out, hipStream_t s);
 hipError_t launch_bins_last_row(const tfft_bin* bins, uint64_t n, int PH, int PW, int* last_row, hipStream_t s);
 hipError_t launch_embed(float2* spec, const tfft_bin* bins, const uint8_t* bits, const float* jitter,
                         const EmbedParams& P, int n_images, int* err, hipStream_t s);

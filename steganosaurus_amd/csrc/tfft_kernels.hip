@@ -902,7 +902,9 @@ __device__ __forceinline__ unsigned frame_bit(const uint8_t* __restrict__ header
 // FULL: every output element of the launch exists (all columns, groups and rows < out_rows): the stores carry no predicate.  A store
 //       behind an exec-mask branch may or may not have been issued, so s_waitcnt cannot count past it: the wait for the prefetched
 //       tile that follows then also waits for the stores just issued (their whole latency, every tile).  The launcher picks it.
-template <int LOGL, int SIGN, int MODE = COLS_PLAIN, bool DC = false, bool TW = false, bool FULL = false>
+// PH: the phase options of the batched calls (ColParams::em_jp / em_med, tfft_set_phase_options) are compiled in -- COLS_EMBED and
+//     COLS_READ only, their own instantiations, so that the fixed-alpha kernels stay exactly as they are (registers, occupancy)
+template <int LOGL, int SIGN, int MODE = COLS_PLAIN, bool DC = false, bool TW = false, bool FULL = false, bool PH = false>
 __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE == COLS_EMIT && TFFT_COLS_PFEMIT) ? 1 : (FULL ? TFFT_COLS_WAVES(LOGL) : imin(2, TFFT_COLS_WAVES(LOGL)))) k_fft_cols(const float2* in, float2* out, const float2* __restrict__ tw,
                            ColParams P) {
     constexpr int L = 1 << LOGL, E = elems_for(L), T = L / E, C = 16;
@@ -1080,9 +1082,14 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
             if (with_value) { en[i].f = em_fl[ec]; en[i].bit = em_pb[ec]; }
         }
     };
-    auto em_delta = [&](float2 f, unsigned bit, unsigned conj) -> float2 {      // write_bit_on_bin S:712-732 minus the old value
+    // adaptive alpha (S:704-710): this image's median of the plane (workgroup uniform)
+    const float em_medp = (MODE == COLS_EMBED && PH && P.em_med) ? fmaxf(1e-12f, P.em_med[3 * img + plane]) : 1.f;
+    auto em_delta = [&](float2 f, unsigned bit, unsigned conj, unsigned e) -> float2 {      // write_bit_on_bin S:712-732 minus the old value
         const float mag = fmaxf(1e-12f, mag_of(f));
-        float2 nv = make_float2(mag * P.em_cos, bit ? mag * P.em_sin : -mag * P.em_sin);
+        float ca = P.em_cos, sa = P.em_sin;
+        if (PH && P.em_med) sincosf(P.em_alpha * fminf(2.f, fmaxf(0.5f, mag / em_medp)), &sa, &ca);
+        float2 nv = make_float2(mag * ca, bit ? mag * sa : -mag * sa);
+        if (PH && P.em_jp) nv = cmul(nv, P.em_jp[e]);     // polar(mag, +-a + jitter[bit]): the phase of +-a turned by the bin's jitter
         if (conj) nv = cconj(nv);
         return csub(nv, f);
     };
@@ -1156,9 +1163,12 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
 #pragma unroll
                 for (int m = 0; m < E; m++) lds[lay.idx(t + m * T, c)] = make_float2(0.f, 0.f);
                 lds_barrier();
+                unsigned pe0 = 0;       // (PH: the first entry of the tile, for the jitter phasors of the entries in registers)
+                if (PH) { unsigned pe1; em_range(tile, pe0, pe1); }
 #pragma unroll
                 for (int i = 0; i < NE; i++)
-                    if (enC[i].live && enC[i].bit < 2u) lds[lay.idx(enC[i].tb.k, enC[i].tb.c)] = em_delta(enC[i].f, enC[i].bit, enC[i].tb.conj);
+                    if (enC[i].live && enC[i].bit < 2u)
+                        lds[lay.idx(enC[i].tb.k, enC[i].tb.c)] = em_delta(enC[i].f, enC[i].bit, enC[i].tb.conj, pe0 + (unsigned)(em_tid + i * em_nthr));
                 if (g < P.G) {          // a bucket with more than NE entries per thread: the rest the slow way
                     unsigned e0, e1;
                     em_range(tile, e0, e1);
@@ -1166,7 +1176,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
                         const TileBin tb = P.rd_bins[e];
                         const unsigned bit = em_pb[e];
                         if (bit >= 2u) continue;
-                        lds[lay.idx(tb.k, tb.c)] = em_delta(em_fl[e], bit, tb.conj);
+                        lds[lay.idx(tb.k, tb.c)] = em_delta(em_fl[e], bit, tb.conj, e);
                     }
                 }
                 lds_barrier();
@@ -1233,9 +1243,16 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
                 unsigned e0, e1;
                 em_range(tile, e0, e1);
                 uint8_t* bo = P.rd_bits + (size_t)img * P.rd_n;
-                auto bit_of = [&](const TileBin tb) -> uint8_t {       // read_bit_from_bin S:734-746 for a fixed alpha in (0, pi), no jitter: Im >= 0
+                // read_bit_from_bin S:734-746 for an alpha in (0, pi): Im >= 0; with jitter j the targets j +- a are symmetric about j,
+                // so the bit is Im(F e^{-ij}) >= 0
+                auto bit_of = [&](const TileBin tb, unsigned e) -> uint8_t {
                     float2 v = lds[lay.idx(tb.k, tb.c)];
                     if (DC) v = cadd(v, cmul(lds_ah[tb.k], lds_aw[tb.c]));
+                    if (PH && P.em_jp) {
+                        const float2 p = P.em_jp[e];
+                        if (tb.conj) v = cconj(v);
+                        return (uint8_t)(v.y * p.x - v.x * p.y >= 0.0f ? 1 : 0);
+                    }
                     return (uint8_t)((tb.conj ? -v.y : v.y) >= 0.0f ? 1 : 0);
                 };
                 // stores without a predicate (see FULL): a lane without an entry writes its byte to the context's scratch line instead
@@ -1243,9 +1260,9 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
                 for (int i = 0; i < NE; i++) {
                     const TileBin tb = enC[i].tb;
                     uint8_t* dst = enC[i].live ? bo + tb.bit : P.trash + em_tid;
-                    *dst = bit_of(tb);
+                    *dst = bit_of(tb, enC[i].live ? e0 + (unsigned)(em_tid + i * em_nthr) : 0u);
                 }
-                for (unsigned e = e0 + (unsigned)(em_tid + NE * em_nthr); e < e1; e += em_nthr) { const TileBin tb = P.rd_bins[e]; bo[tb.bit] = bit_of(tb); }
+                for (unsigned e = e0 + (unsigned)(em_tid + NE * em_nthr); e < e1; e += em_nthr) { const TileBin tb = P.rd_bins[e]; bo[tb.bit] = bit_of(tb, e); }
             }
             lds_barrier();            // before the next tile's exchanges overwrite the parked values
             if (PF) {
@@ -1557,7 +1574,8 @@ __global__ void k_embed(float2* __restrict__ spec, const tfft_bin* __restrict__ 
         nv = make_float2(mag * P.cos_a, bit ? mag * P.sin_a : -mag * P.sin_a);
     } else {
         double alpha = P.alpha;
-        if (P.adaptive) alpha *= fmin(2.0, fmax(0.5, (double)mag / fmax(1e-12, P.med[p])));   // S:704-710
+        const double med = P.med_dev ? (double)P.med_dev[3 * img + p] : P.med[p];
+        if (P.adaptive) alpha *= fmin(2.0, fmax(0.5, (double)mag / fmax(1e-12, med)));   // S:704-710
         const double theta = (bit ? alpha : -alpha) + (jitter ? (double)jitter[j] : 0.0);
         nv = make_float2((float)((double)mag * cos(theta)), (float)((double)mag * sin(theta)));
     }
@@ -1576,6 +1594,16 @@ __global__ void k_gather_bits(const TileBin* __restrict__ ent, const unsigned* _
     unsigned b = 2u;
     if (j < limit) b = hdr ? frame_bit(hdr + (size_t)img * 38, pay + (size_t)img * plen, j) : (unsigned)(bits[(size_t)img * n + j] & 1u);
     out[(size_t)img * n + e] = (uint8_t)b;
+}
+
+// jitter of the batched calls in bucket order (tfft_set_phase_options): one unit phasor per bucket entry, shared by every image
+__global__ void k_gather_jitter(const TileBin* __restrict__ ent, const unsigned* __restrict__ n_ent, const float* __restrict__ jitter, uint64_t n,
+                                float2* __restrict__ out) {
+    const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= *n_ent) return;
+    const uint64_t j = ent[e].bit;
+    const double jt = j < n ? (double)jitter[j] : 0.0;
+    out[e] = make_float2((float)cos(jt), (float)sin(jt));
 }
 
 // read_bit_from_bin S:734-746 for one (already conjugate-corrected) bin value
@@ -2760,7 +2788,7 @@ hipError_t launch_rows_inv(const float2* in, uint8_t* rgb, const float2* tw_pw, 
     return hipSuccess;
 }
 
-template <int LOGL, int SIGN, int MODE = COLS_PLAIN, bool DC = false, bool TW = false, bool FULL = false>
+template <int LOGL, int SIGN, int MODE = COLS_PLAIN, bool DC = false, bool TW = false, bool FULL = false, bool PH = false>
 static hipError_t launch_cols_t(const float2* in, float2* out, const float2* tw, const ColParams& P, int n_planes,
                                 hipStream_t s) {
     constexpr int L = 1 << LOGL, E = elems_for(L), T = L / E, C = 16;
@@ -2775,7 +2803,7 @@ static hipError_t launch_cols_t(const float2* in, float2* out, const float2* tw,
         // only for the statistics, whose classification / histogram live in that store loop)
         const int rows_out_max = P.out_a * (L - 1) + P.out_b * (P.G - 1);
         if ((LOGL >= 6 || MODE == COLS_STAT || P.hist_sel) && rows_out_max < P.out_rows && P.M % C == 0 && Geff % gpb == 0)
-            return launch_cols_t<LOGL, SIGN, MODE, DC, TW, true>(in, out, tw, P, n_planes, s);
+            return launch_cols_t<LOGL, SIGN, MODE, DC, TW, true, PH>(in, out, tw, P, n_planes, s);
         if (MODE == COLS_STAT) return hipErrorInvalidValue;      // the in-register classification lives in the unpredicated store loop only
     }
     const size_t lds0 = (size_t)gpb * L * C * sizeof(float2) + (DC ? (size_t)gpb * L * sizeof(float2) : 0) + (TW ? (size_t)gpb * L * sizeof(float2) : 0) +
@@ -2806,7 +2834,7 @@ static hipError_t launch_cols_t(const float2* in, float2* out, const float2* tw,
         if (fixed + (size_t)P.PH * (P.M + 1) > P.st_cand_stride) return hipErrorInvalidValue;
         Q.st_cand_fixed = (unsigned)fixed;
     }
-    auto k = k_fft_cols<LOGL, SIGN, MODE, DC, TW, FULL>;
+    auto k = k_fft_cols<LOGL, SIGN, MODE, DC, TW, FULL, PH>;
     if (lds_total > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_total);
         if (e != hipSuccess) return e;
@@ -2825,6 +2853,10 @@ hipError_t launch_cols(const float2* in, float2* out, const float2* tw_ph, const
     if (P.st_sel && (!P.em_on || sign < 0 || logl > 9 || logl < 4 || !P.st_cand || !P.st_col0 || (P.st_cap && (!P.st_partial || !P.st_amb)))) return hipErrorInvalidValue;
     if ((P.tile_step > 1 || P.gate) && (sign < 0 || P.rd_bins || P.last_row_dev || P.tw_out)) return hipErrorInvalidValue;      // plain final forward step only       // the bucket modes redirect the stores of idle lanes to the context's scratch line
     if (P.em_m2 && sign > 0 && (!P.em_on || !P.st_col0)) return hipErrorInvalidValue;      // (the inverse step ignores it)
+    // the phase options exist in the first inverse step (COLS_EMBED) and the tile-resident read (COLS_READ) only
+    if ((P.em_jp || P.em_med) && !((sign < 0 && P.em_on) || (sign > 0 && P.rd_bins && !P.em_on))) return hipErrorInvalidValue;
+    if (P.em_med && sign > 0) return hipErrorInvalidValue;
+    const bool phase = P.em_jp || P.em_med;
 #define G(n, MODE)                                                                      \
     (P.dc_ah ? launch_cols_t<(n <= 9 ? n : 9), +1, MODE, true>(in, out, tw_ph, P, n_planes, s) \
              : launch_cols_t<(n <= 9 ? n : 9), +1, MODE, false>(in, out, tw_ph, P, n_planes, s))
@@ -2832,17 +2864,24 @@ hipError_t launch_cols(const float2* in, float2* out, const float2* tw_ph, const
     (P.tw_out ? launch_cols_t<(n <= 9 ? n : 9), -1, COLS_PLAIN, DCF, true>(in, out, tw_ph, P, n_planes, s) \
               : launch_cols_t<(n <= 9 ? n : 9), -1, COLS_PLAIN, DCF, false>(in, out, tw_ph, P, n_planes, s))
 #define GE(n)                                                                      \
-    (P.tw_out ? launch_cols_t<(n <= 9 ? n : 9), -1, COLS_EMBED, false, true>(in, out, tw_ph, P, n_planes, s) \
-              : launch_cols_t<(n <= 9 ? n : 9), -1, COLS_EMBED, false, false>(in, out, tw_ph, P, n_planes, s))
+    (phase ? (P.tw_out ? launch_cols_t<(n <= 9 ? n : 9), -1, COLS_EMBED, false, true, false, true>(in, out, tw_ph, P, n_planes, s) \
+                       : launch_cols_t<(n <= 9 ? n : 9), -1, COLS_EMBED, false, false, false, true>(in, out, tw_ph, P, n_planes, s)) \
+           : P.tw_out ? launch_cols_t<(n <= 9 ? n : 9), -1, COLS_EMBED, false, true>(in, out, tw_ph, P, n_planes, s) \
+                      : launch_cols_t<(n <= 9 ? n : 9), -1, COLS_EMBED, false, false>(in, out, tw_ph, P, n_planes, s))
+#define GR(n)                                                                      \
+    (!P.em_jp ? G(n, COLS_READ)                                                    \
+              : P.dc_ah ? launch_cols_t<(n <= 9 ? n : 9), +1, COLS_READ, true, false, false, true>(in, out, tw_ph, P, n_planes, s) \
+                        : launch_cols_t<(n <= 9 ? n : 9), +1, COLS_READ, false, false, false, true>(in, out, tw_ph, P, n_planes, s))
 #define F(n)                                                                            \
     return sign < 0 ? (P.em_on ? GE(n) : P.dc_ah ? GI(n, true) : GI(n, false)) \
          : P.tw_out ? launch_cols_t<(n <= 9 ? n : 9), +1, COLS_PLAIN, false, true>(in, out, tw_ph, P, n_planes, s) \
-         : (P.em_on && P.st_sel) ? G(n, COLS_STAT) : P.em_on ? G(n, COLS_EMIT) : P.rd_bins ? G(n, COLS_READ) : P.last_row_dev ? G(n, COLS_ROWLIMIT) : G(n, COLS_PLAIN)
+         : (P.em_on && P.st_sel) ? G(n, COLS_STAT) : P.em_on ? G(n, COLS_EMIT) : P.rd_bins ? GR(n) : P.last_row_dev ? G(n, COLS_ROWLIMIT) : G(n, COLS_PLAIN)
     TFFT_DISPATCH_LOG(logl, F)
 #undef F
 #undef G
 #undef GI
 #undef GE
+#undef GR
     return hipSuccess;
 }
 
@@ -2869,6 +2908,11 @@ hipError_t launch_gather_bits(const TileBin* ent, const unsigned* n_ent, const u
                               uint64_t n, uint64_t limit, int n_images, uint8_t* out, hipStream_t s) {
     if (n == 0 || n_images == 0) return hipSuccess;
     hipLaunchKernelGGL(k_gather_bits, dim3((unsigned)((n + 255) / 256), n_images), dim3(256), 0, s, ent, n_ent, bits, hdr, pay, plen, n, limit, out);
+    return hipGetLastError();
+}
+hipError_t launch_gather_jitter(const TileBin* ent, const unsigned* n_ent, const float* jitter, uint64_t n, float2* out, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_gather_jitter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ent, n_ent, jitter, n, out);
     return hipGetLastError();
 }
 hipError_t launch_bins_last_row(const tfft_bin* bins, uint64_t n, int PH, int PW, int* last_row, hipStream_t s) {
