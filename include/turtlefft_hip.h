@@ -117,7 +117,7 @@ int tfft_capacity(tfft_ctx* ctx, int slot, double rmin, double rmax, const doubl
  * _dev variant that buffer must still be alive): 192 inner products, no transform,
  * so the reference's quantiser floor(log(1+mag)/2) (S:433) sees its own values to
  * ~1e-13 and the 32-byte cover hash is the reference's.  TFFT_E_STATE after a batch
- * call (no single image belongs to the slot).  Synchronises. */
+ * call (no single image belongs to the slot: tfft_lowfreq_mag_batch_dev serves batches).  Synchronises. */
 int tfft_lowfreq_mag(tfft_ctx* ctx, int slot, int region, double* out);
 
 /* ------------------------------------------------------------- embed / read
@@ -243,6 +243,46 @@ int tfft_extract_stream_batch(tfft_ctx* ctx, int n_images, const uint8_t* rgb, i
 void* tfft_host_alloc(size_t bytes);
 void tfft_host_free(void* p);
 
+/* ------------------------------------------------------ one walk per image
+ * The stream pipelines above for batches whose images do NOT share a walk: images with their own passphrase or key, and
+ * --cover_dependent_path 1 (path_key = SHA256(pass | key || cover_hash), S:1020-1039), where every cover has its own walk even under one
+ * passphrase.  Semantics as tfft_*_stream_batch[_dev], image by image, with these differences:
+ *   bins     : n_images walks of n_bins positions each, image i's at bins + i*n_bins, in WALK (= stream) order (not sorted: there is no
+ *              bit index; every entry's stream position is its place in the image's own list);
+ *   jitter   : n_images*n_bins floats in the same layout (tfft_walk_jitter of each image's own plane keys), or NULL (no jitter);
+ *   adaptive : adaptive alpha (S:704-710) with each image's own medians, the rules of tfft_set_phase_options (extraction: |alpha| >= pi/2
+ *              gives TFFT_E_INVALID);
+ *   the context's shared-list state does not mix with these calls: with a bit index (tfft_set_bit_index) or a phase-option jitter array
+ *   (tfft_set_phase_options) set they return TFFT_E_STATE (the context's adaptive flag is ignored: `adaptive` rules);
+ *   a bin outside the grid or on an excluded axis in any image's list gives TFFT_E_BIN_RANGE: the _dev forms synchronise with the
+ *   context's stream at their end to report it;
+ *   the buckets of the tile-resident kernels are built from the lists on every call; no launch sequence is captured into or replayed
+ *   from the graph cache (TFFT_GRAPHS), and tfft_bins_register_dev does not apply;
+ *   n_slots * n_bins must stay below 2^32 (else TFFT_E_TOO_LARGE).
+ * The host forms run the three-stream pipeline of tfft_*_stream_batch: lists and jitter travel per part of the ring with the images
+ * (8 + 4 bytes per position and image).  Crypto stays with the caller (libtfhost / the CLI): HKDF, the cover-hash quantiser. */
+int tfft_embed_stream_batch_walks_dev(tfft_ctx* ctx, int n_images, const void* rgb_dev, int w, int h, int center,
+                                      const void* bins_dev, const void* jitter_dev, uint64_t n_bins, int adaptive,
+                                      const void* header_dev, const void* payload_dev, uint64_t payload_len,
+                                      double alpha, double rmin, double rmax, double magmin, void* usable_out_dev, void* rgb_out_dev);
+int tfft_extract_stream_batch_walks_dev(tfft_ctx* ctx, int n_images, const void* rgb_dev, int w, int h, int center,
+                                        const void* bins_dev, const void* jitter_dev, uint64_t n_bins, int adaptive, double alpha,
+                                        void* header_out_dev, void* payload_out_dev, uint64_t max_payload_len, void* status_out_dev,
+                                        void* raw_bits_out_dev);
+int tfft_embed_stream_batch_walks(tfft_ctx* ctx, int n_images, const uint8_t* rgb, int w, int h, int center, const tfft_bin* bins,
+                                  const float* jitter, uint64_t n_bins, int adaptive, const uint8_t* header, const uint8_t* payload,
+                                  uint64_t payload_len, double alpha, double rmin, double rmax, double magmin,
+                                  uint64_t* usable_out /* or NULL */, uint8_t* rgb_out);
+int tfft_extract_stream_batch_walks(tfft_ctx* ctx, int n_images, const uint8_t* rgb, int w, int h, int center, const tfft_bin* bins,
+                                    const float* jitter, uint64_t n_bins, int adaptive, double alpha, uint8_t* header_out,
+                                    uint8_t* payload_out, uint64_t max_payload_len, int32_t* status_out,
+                                    uint8_t* raw_bits_out /* or NULL */);
+/* compute_cover_hash's magnitudes (S:428-436) for the n_images images of a batch (device pointers, image i at rgb + i*w*h*3):
+ * out = n_images*3*region*region doubles, image i's at out + i*3*region*region -- the same values, bit for bit, as tfft_lowfreq_mag on
+ * each image alone (same kernels, same summation order).  Needs no forward call and leaves the slots alone; does not synchronise.
+ * The quantiser + SHA-256 of the hash stay with the caller (libtfhost: tfh_cover_hash_from_mags). */
+int tfft_lowfreq_mag_batch_dev(tfft_ctx* ctx, int n_images, const void* rgb_dev, int w, int h, int center, int region, void* out_dev);
+
 /* --------------------------------------------------------- keyed walk (HOST)
  * KS + Turtle + the density gate (S:665-695, S:749-810, S:1076-1081): a
  * resumable generator of embedding positions.  Pure host code, no device.
@@ -260,6 +300,13 @@ int tfft_walk_destroy(tfft_walk* w);
  * the plane's own keystream (keys_rgb = 3*32 bytes key_r|key_g|key_b) in list
  * order; two bytes are consumed per bin even when max_jitter == 0 (S:719). */
 int tfft_walk_jitter(const uint8_t keys_rgb[96], const tfft_bin* bins, uint64_t n, double max_jitter, float* out);
+/* n walks at once, for the per-image batch calls: keys = n*128 bytes, image i's walk key and R, G, B jitter keys at keys + 128*i
+ * (key_walk | key_r | key_g | key_b, S:1054-1063).  bins_out (n*n_bins) and jitter_out (n*n_bins floats, or NULL) receive what
+ * tfft_walk_create + tfft_walk_next(n_bins) + tfft_walk_jitter give for each key, bit for bit; status_out[i] = TFFT_OK or
+ * TFFT_E_EXHAUSTED (that image's remaining positions and jitter are zero).  The walks run on up to n_threads threads (the caller sizes
+ * the pool).  Returns TFFT_OK, or the first failing image's status. */
+int tfft_walks_build(int n, const uint8_t* keys, int ph, int pw, double rmin, double rmax, double density, double max_jitter,
+                     uint64_t n_bins, int n_threads, tfft_bin* bins_out, float* jitter_out, int32_t* status_out);
 
 /* ------------------------------------------------------- bin visiting order
  * (new; no counterpart in the reference, whose loop S:1074-1097 visits the

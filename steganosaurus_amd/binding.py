@@ -73,6 +73,12 @@ SYMBOLS = {
     "tfft_set_bit_index": (_i, [_vp, _vp, _u64]),
     "tfft_bins_register_dev": (_i, [_vp, _vp, _u64]),
     "tfft_set_phase_options": (_i, [_vp, _vp, _u64, _i]),
+    "tfft_embed_stream_batch_walks_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _u64, _i, _vp, _vp, _u64, _d, _d, _d, _d, _vp, _vp]),
+    "tfft_extract_stream_batch_walks_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _u64, _i, _d, _vp, _vp, _u64, _vp, _vp]),
+    "tfft_embed_stream_batch_walks": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _u64, _i, _vp, _vp, _u64, _d, _d, _d, _d, _vp, _vp]),
+    "tfft_extract_stream_batch_walks": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _u64, _i, _d, _vp, _vp, _u64, _vp, _vp]),
+    "tfft_lowfreq_mag_batch_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "tfft_walks_build": (_i, [_i, _vp, _i, _i, _d, _d, _d, _d, _u64, _i, _vp, _vp, _vp]),
     "tfft_profile_stage": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _u64, _d, C.POINTER(C.c_float), _pi]),
     "tfft_timer_begin": (_i, [_vp]),
     "tfft_timer_end": (_i, [_vp, C.POINTER(C.c_float)]),
@@ -171,6 +177,24 @@ def walk_jitter(keys_rgb: bytes, bins, max_jitter, lib=None):
     out = np.zeros(len(bins), np.float32)
     _check(lib.tfft_walk_jitter(keys_rgb, _ptr(bins), len(bins), max_jitter, _ptr(out)), "tfft_walk_jitter")
     return out
+
+
+def walks_build(keys, ph, pw, n_bins, max_jitter=None, rmin=0.05, rmax=0.45, density=0.7, n_threads=16, lib=None):
+    """One walk per image (tfft_walks_build): keys = n*128 bytes (walk | r | g | b subkeys per image).  Returns bins (n, n_bins)
+    BIN_DTYPE, jitter (n, n_bins) float32 or None (max_jitter None: no jitter), status (n,) int32 (0, or -7 for an exhausted walk)."""
+    lib = lib or load()
+    keys = bytes(keys)
+    assert len(keys) % 128 == 0
+    n = len(keys) // 128
+    bins = np.zeros((n, n_bins), BIN_DTYPE)
+    jit = np.zeros((n, n_bins), np.float32) if max_jitter is not None else None
+    status = np.zeros(n, np.int32)
+    kb = np.frombuffer(keys, np.uint8).copy()
+    rc = lib.tfft_walks_build(n, _ptr(kb), ph, pw, rmin, rmax, density, float(max_jitter or 0.0), n_bins, n_threads, _ptr(bins),
+                              _ptr(jit), _ptr(status))
+    if rc not in (TFFT_OK, -7):
+        _check(rc, "tfft_walks_build")
+    return bins, jit, status
 
 
 def bins_sort(bins, lib=None):
@@ -353,6 +377,44 @@ class Context:
         _check(self.lib.tfft_extract_stream_batch_dev(self.h, n_images, _ptr(rgb_ptr), w, h, int(center), _ptr(bins_ptr), n_bins, alpha,
                                                       _ptr(header_out_ptr), _ptr(payload_out_ptr), max_payload_len, _ptr(status_out_ptr),
                                                       _ptr(raw_bits_out_ptr)), "tfft_extract_stream_batch_dev")
+
+    # ---- one walk per image (own keys, cover-dependent paths) ------------------------------------------------------
+    def embed_stream_batch_walks_dev(self, n_images, rgb_ptr, w, h, bins_ptr, jitter_ptr, n_bins, header_ptr, payload_ptr, payload_len,
+                                     out_ptr, adaptive=False, alpha=0.5, center=False, rmin=0.05, rmax=0.45, magmin=0.01, usable_ptr=None):
+        _check(self.lib.tfft_embed_stream_batch_walks_dev(self.h, n_images, _ptr(rgb_ptr), w, h, int(center), _ptr(bins_ptr), _ptr(jitter_ptr),
+                                                          n_bins, int(adaptive), _ptr(header_ptr), _ptr(payload_ptr), payload_len, alpha, rmin,
+                                                          rmax, magmin, _ptr(usable_ptr), _ptr(out_ptr)), "tfft_embed_stream_batch_walks_dev")
+
+    def extract_stream_batch_walks_dev(self, n_images, rgb_ptr, w, h, bins_ptr, jitter_ptr, n_bins, header_out_ptr, payload_out_ptr,
+                                       max_payload_len, status_out_ptr, raw_bits_out_ptr=None, adaptive=False, alpha=0.5, center=False):
+        _check(self.lib.tfft_extract_stream_batch_walks_dev(self.h, n_images, _ptr(rgb_ptr), w, h, int(center), _ptr(bins_ptr), _ptr(jitter_ptr),
+                                                            n_bins, int(adaptive), alpha, _ptr(header_out_ptr), _ptr(payload_out_ptr),
+                                                            max_payload_len, _ptr(status_out_ptr), _ptr(raw_bits_out_ptr)),
+               "tfft_extract_stream_batch_walks_dev")
+
+    def embed_stream_batch_walks_host(self, rgb, bins, header, payload, out, jitter=None, adaptive=False, usable=None, alpha=0.5,
+                                      center=False, rmin=0.05, rmax=0.45, magmin=0.01):
+        """rgb/out: (n,H,W,3) uint8; bins: (n, n_bins) BIN_DTYPE; jitter: (n, n_bins) float32 or None"""
+        n, h, w = rgb.shape[:3]
+        bins = np.ascontiguousarray(bins, BIN_DTYPE)
+        jit = None if jitter is None else np.ascontiguousarray(jitter, np.float32)
+        _check(self.lib.tfft_embed_stream_batch_walks(self.h, n, _ptr(rgb), w, h, int(center), _ptr(bins), _ptr(jit), bins.shape[1], int(adaptive),
+                                                      _ptr(header), _ptr(payload), payload.shape[1] if payload is not None else 0, alpha, rmin,
+                                                      rmax, magmin, _ptr(usable), _ptr(out)), "tfft_embed_stream_batch_walks")
+
+    def extract_stream_batch_walks_host(self, rgb, bins, header_out, payload_out, status_out, raw_bits_out=None, jitter=None, adaptive=False,
+                                        alpha=0.5, center=False):
+        n, h, w = rgb.shape[:3]
+        bins = np.ascontiguousarray(bins, BIN_DTYPE)
+        jit = None if jitter is None else np.ascontiguousarray(jitter, np.float32)
+        _check(self.lib.tfft_extract_stream_batch_walks(self.h, n, _ptr(rgb), w, h, int(center), _ptr(bins), _ptr(jit), bins.shape[1],
+                                                        int(adaptive), alpha, _ptr(header_out), _ptr(payload_out), payload_out.shape[1],
+                                                        _ptr(status_out), _ptr(raw_bits_out)), "tfft_extract_stream_batch_walks")
+
+    def lowfreq_mag_batch_dev(self, n_images, rgb_ptr, w, h, region, out_ptr, center=False):
+        """compute_cover_hash's magnitudes of n images: out = n*3*region*region doubles (device)"""
+        _check(self.lib.tfft_lowfreq_mag_batch_dev(self.h, n_images, _ptr(rgb_ptr), w, h, int(center), region, _ptr(out_ptr)),
+               "tfft_lowfreq_mag_batch_dev")
 
     STAGES = ["rows_fwd", "cols_fwd_a", "cols_fwd_b", "embed", "cols_inv_a", "cols_inv_b", "rows_inv", "read",
               "medians", "capacity", "cols_fwd_read"]

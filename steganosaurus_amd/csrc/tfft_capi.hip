@@ -225,7 +225,7 @@ int get_dc_table(tfft_ctx* c, int valid, int N, int center, int kind, double sca
 void invalidate_graphs(tfft_ctx* c);      // cached launch sequences hold raw device pointers: dropped whenever a buffer is reallocated
 
 static void copy_embed_fields(ColParams& cp, const ColParams& e, bool inverse) {
-    cp.rd_bins = e.rd_bins; cp.rd_off = e.rd_off; cp.trash = e.trash;
+    cp.rd_bins = e.rd_bins; cp.rd_off = e.rd_off; cp.trash = e.trash; cp.rd_walks = e.rd_walks;
     cp.em_n = e.em_n; cp.em_cos = e.em_cos; cp.em_sin = e.em_sin; cp.em_fl = e.em_fl; cp.em_pb = e.em_pb; cp.em_on = 1; cp.em_m2 = e.em_m2;
     if (inverse) { cp.em_jp = e.em_jp; cp.em_med = e.em_med; cp.em_alpha = e.em_alpha; }      // (the phase options belong to COLS_EMBED)
     cp.st_sel = e.st_sel; cp.st_cand = e.st_cand; cp.st_cand_stride = e.st_cand_stride; cp.st_partial = e.st_partial; cp.st_amb = e.st_amb;
@@ -282,7 +282,7 @@ int enqueue_fft_stage(tfft_ctx* c, int s0, int n, int stage, const uint8_t* rgb_
                 rc = get_dc_table(c, s.H, s.PH, s.center, 0, (double)c->dc_bias, &cp.dc_ah); if (rc) return rc;
                 rc = get_dc_table(c, s.W, s.PWi, s.center, 1, 1.0, &cp.dc_aw); if (rc) return rc;
             }
-                if (md.fwd_read) { const ColParams& r = *md.fwd_read; cp.rd_bins = r.rd_bins; cp.rd_off = r.rd_off; cp.rd_bits = r.rd_bits; cp.rd_n = r.rd_n; cp.em_jp = r.em_jp; cp.trash = c->trash; cp.tiles_per_block = c->cols_tiles_read; }
+                if (md.fwd_read) { const ColParams& r = *md.fwd_read; cp.rd_bins = r.rd_bins; cp.rd_off = r.rd_off; cp.rd_bits = r.rd_bits; cp.rd_n = r.rd_n; cp.em_jp = r.em_jp; cp.rd_walks = r.rd_walks; cp.trash = c->trash; cp.tiles_per_block = c->cols_tiles_read; }
                 else if (md.fwd_emit) { copy_embed_fields(cp, *md.fwd_emit, false); if (!c->cols_tiles_forced && pl.log_n2 <= 8) cp.tiles_per_block = 2; if (cp.st_sel && c->cols_tiles_stat) cp.tiles_per_block = c->cols_tiles_stat; }
                 else if (md.fwd_plain_extra) copy_plain_extra(cp, *md.fwd_plain_extra);
                 HIPCHK(c, launch_cols(tmp, md.fwd_out_override ? md.fwd_out_override : spec, tw_h, cp, pl.log_n2, +1, 3 * n, st));
@@ -300,7 +300,7 @@ int enqueue_fft_stage(tfft_ctx* c, int s0, int n, int stage, const uint8_t* rgb_
                 rc = get_dc_table(c, s.H, s.PH, s.center, 0, (double)c->dc_bias, &cp.dc_ah); if (rc) return rc;
                 rc = get_dc_table(c, s.W, s.PWi, s.center, 1, 1.0, &cp.dc_aw); if (rc) return rc;
             }
-            if (md.fwd_read) { const ColParams& r = *md.fwd_read; cp.rd_bins = r.rd_bins; cp.rd_off = r.rd_off; cp.rd_bits = r.rd_bits; cp.rd_n = r.rd_n; cp.em_jp = r.em_jp; cp.trash = c->trash; cp.tiles_per_block = c->cols_tiles_read; }
+            if (md.fwd_read) { const ColParams& r = *md.fwd_read; cp.rd_bins = r.rd_bins; cp.rd_off = r.rd_off; cp.rd_bits = r.rd_bits; cp.rd_n = r.rd_n; cp.em_jp = r.em_jp; cp.rd_walks = r.rd_walks; cp.trash = c->trash; cp.tiles_per_block = c->cols_tiles_read; }
             else if (md.fwd_emit) { copy_embed_fields(cp, *md.fwd_emit, false); if (!c->cols_tiles_forced && pl.log_n2 <= 8) cp.tiles_per_block = 2; if (cp.st_sel && c->cols_tiles_stat) cp.tiles_per_block = c->cols_tiles_stat; }
                 else if (md.fwd_plain_extra) copy_plain_extra(cp, *md.fwd_plain_extra);
             HIPCHK(c, launch_cols(tmp, md.fwd_out_override ? md.fwd_out_override : spec, tw_h, cp, pl.log_n2, +1, 3 * n, st));
@@ -1280,17 +1280,46 @@ static int enqueue_forward_tilestats(tfft_ctx* c, int s0, int g, const uint8_t* 
 }
 
 struct FrameSrc { const uint8_t* hdr; const uint8_t* pay; uint64_t plen; };      // packed frames of a chunk (device), image i at hdr + 38*i / pay + plen*i
+// one walk per image (tfft_*_stream_batch_walks*): the chunk's `bins` are g lists of n_bits, image i's at bins + i*n_bits; jitter (device, the
+// same layout, or nullptr) and adaptive alpha come with them instead of from the context's phase options
+struct WalkSrc { const float* jit; int adaptive; };
+// the per-image lists of a chunk bucketed (launch_bucket_walks) on compute stream `which`: the shared-list buckets there are gone
+static int build_buckets_walks(tfft_ctx* c, int which, const tfft_bin* bins, uint64_t n_bits, int g, const Slot& s, int G, const float* jit,
+                               hipStream_t st) {
+    const int ntiles = (s.PWi / 2 + 15) / 16, nbt = 3 * ntiles * G * g + 1;      // (+ the invalid bins' bucket)
+    if ((uint64_t)g * n_bits > 0xFFFFFFFFull || (uint64_t)3 * ntiles * G * g + 1 > 1024ull * 1024ull) return TFFT_E_TOO_LARGE;
+    int rc = ensure_buckets(c, which, (uint64_t)g * n_bits, nbt);
+    if (rc) return rc;
+    auto& tb = c->tb[which];
+    if (tb.built_for) c->graphs_stale = true;      // a sequence captured for a registered list left its bucket build out
+    tb.built_for = nullptr; tb.jp_for = 0; tb.row_for = nullptr;
+    HIPCHK(c, launch_bucket_walks(bins, n_bits, g, s.PH, s.PWi, G, tb.cnt, tb.off, tb.ent, c->err, st));
+    if (!jit) return TFFT_OK;
+    const uint64_t need = (uint64_t)g * n_bits;
+    if (need > tb.jp_cap || !tb.jp) {
+        (void)hipStreamSynchronize(c->stream);
+        if (c->stream2) (void)hipStreamSynchronize(c->stream2);
+        invalidate_graphs(c);
+        (void)hipFree(tb.jp); tb.jp = nullptr; tb.jp_cap = 0;
+        const uint64_t cap = need + need / 4 + 1024;
+        if (dev_alloc(c, (void**)&tb.jp, cap * sizeof(float2))) return TFFT_E_NOMEM;
+        tb.jp_cap = cap;
+    }
+    HIPCHK(c, launch_gather_jitter_walks(tb.ent, jit, n_bits, g, tb.jp, st));
+    return TFFT_OK;
+}
 static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, const tfft_bin* bins, const uint8_t* bits,
                             uint64_t n_bits, double alpha, double rmin, double rmax, double magmin,
-                            unsigned long long* usable, uint8_t* rgb_out, hipStream_t st, uint64_t limit, const FrameSrc* frame);
+                            unsigned long long* usable, uint8_t* rgb_out, hipStream_t st, uint64_t limit, const FrameSrc* frame, const WalkSrc* walks);
 static int embed_chunk(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, const tfft_bin* bins, const uint8_t* bits,
                        uint64_t n_bits, double alpha, double rmin, double rmax, double magmin,
-                       unsigned long long* usable, uint8_t* rgb_out, hipStream_t st, uint64_t limit = ~0ull, const FrameSrc* frame = nullptr) {
+                       unsigned long long* usable, uint8_t* rgb_out, hipStream_t st, uint64_t limit = ~0ull, const FrameSrc* frame = nullptr,
+                       const WalkSrc* walks = nullptr) {
     // adaptive alpha needs every image's medians before the embed: the statistics run whether or not the caller asked for the
     // capacities (these then land in the context's own buffer)
-    if (!usable && c->ph_adaptive && n_bits > 0) usable = c->usable + s0;
+    if (!usable && (walks ? walks->adaptive : c->ph_adaptive) && n_bits > 0) usable = c->usable + s0;
     int rc = usable ? stats_clean_if_dirty(c, st) : TFFT_OK;
-    if (!rc) rc = embed_chunk_impl(c, s0, g, rgb_in, bins, bits, n_bits, alpha, rmin, rmax, magmin, usable, rgb_out, st, limit, frame);
+    if (!rc) rc = embed_chunk_impl(c, s0, g, rgb_in, bins, bits, n_bits, alpha, rmin, rmax, magmin, usable, rgb_out, st, limit, frame, walks);
     if (!rc && usable && c->stats_fail_once) {      // test hook (TFFT_STATS_FAIL_ONCE): as if the sequence had broken off -- garbage in the select state, an error out
         c->stats_fail_once = 0;
         HIPCHK(c, hipMemsetAsync(c->sel, 0x01, (size_t)c->n_slots * 3 * sizeof(SelectState), st));
@@ -1301,11 +1330,14 @@ static int embed_chunk(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, const 
 }
 static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, const tfft_bin* bins, const uint8_t* bits,
                             uint64_t n_bits, double alpha, double rmin, double rmax, double magmin,
-                            unsigned long long* usable, uint8_t* rgb_out, hipStream_t st, uint64_t limit, const FrameSrc* frame) {
+                            unsigned long long* usable, uint8_t* rgb_out, hipStream_t st, uint64_t limit, const FrameSrc* frame, const WalkSrc* walks) {
     const Slot& s = c->slots[s0];
     if (!index_ok(c, n_bits) || !phase_ok(c, n_bits)) return TFFT_E_STATE;
-    const bool adaptive = c->ph_adaptive != 0;
-    EmbedParams ep = embed_params(c, s, n_bits, alpha, adaptive, nullptr, c->ph_jit != nullptr);
+    if (walks && (c->bit_index || c->ph_jit)) return TFFT_E_STATE;      // (the shared-list state does not mix with per-image walks)
+    const bool adaptive = walks ? walks->adaptive != 0 : c->ph_adaptive != 0;
+    const float* jit = walks ? walks->jit : c->ph_jit;
+    EmbedParams ep = embed_params(c, s, n_bits, alpha, adaptive, nullptr, jit != nullptr);
+    if (walks) ep.bins_stride = n_bits;
     if (adaptive) ep.med_dev = c->med + 3 * s0;      // (the statistics below run before the embed: see `async`)
     if (limit < n_bits) ep.limit = limit;      // the stream is shorter than the bin list (image i's bits still n_bits apart)
     if (frame) { ep.frame_hdr = frame->hdr; ep.frame_pay = frame->pay; ep.frame_plen = frame->plen; }
@@ -1324,14 +1356,14 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
         const int G = pl.direct ? 1 : (1 << pl.log_n1), ntiles = (s.PWi / 2 + 15) / 16, nb = 3 * ntiles * G;
         rc = ensure_buckets(c, which, n_bits, nb, true);
         if (rc) return rc;
-        rc = build_buckets(c, which, bins, n_bits, s, G, st);
+        rc = walks ? build_buckets_walks(c, which, bins, n_bits, g, s, G, jit, st) : build_buckets(c, which, bins, n_bits, s, G, st);
         if (rc) return rc;
         auto& tb = c->tb[which];
         em.rd_bins = tb.ent; em.rd_off = tb.off; em.trash = c->trash; em.em_fl = tb.fl + (size_t)s0 * n_bits; em.em_pb = tb.pb + (size_t)s0 * n_bits;
-        em.em_n = n_bits; em.em_cos = ep.cos_a; em.em_sin = ep.sin_a;
-        rc = gather_jitter(c, which, n_bits, nb, st);
+        em.em_n = walks ? 0 : n_bits; em.em_cos = ep.cos_a; em.em_sin = ep.sin_a; em.rd_walks = walks ? 1 : 0;      // (walks: entry indices are absolute)
+        if (!walks) rc = gather_jitter(c, which, n_bits, nb, st);
         if (rc) return rc;
-        em.em_jp = c->ph_jit ? tb.jp : nullptr;
+        em.em_jp = jit ? tb.jp : nullptr;
         em.em_med = adaptive ? c->med + 3 * s0 : nullptr; em.em_alpha = (float)alpha;
         if (usable) {
             CapParams p0 = cap_params(c, s, rmin, rmax);
@@ -1341,7 +1373,8 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
         }
         // the stream bits in bucket order (the packed frames of the stream pipelines are expanded on the way).  (On the side stream
         // beside the forward transform it gained nothing measurable: 0.03 ms of 3.3.)
-        HIPCHK(c, launch_gather_bits(tb.ent, tb.off + nb, bits, ep.frame_hdr, ep.frame_pay, ep.frame_plen, n_bits, ep.limit, g, tb.pb + (size_t)s0 * n_bits, st));
+        if (walks) HIPCHK(c, launch_gather_bits_walks(tb.ent, bits, ep.frame_hdr, ep.frame_pay, ep.frame_plen, n_bits, ep.limit, g, tb.pb + (size_t)s0 * n_bits, st));
+        else HIPCHK(c, launch_gather_bits(tb.ent, tb.off + nb, bits, ep.frame_hdr, ep.frame_pay, ep.frame_plen, n_bits, ep.limit, g, tb.pb + (size_t)s0 * n_bits, st));
     }
     if (delta && usable) {
         // the statistics' bracket pass inside the last forward column step: neither the spectrum nor |F|^2 is stored (unless a plane's
@@ -1419,41 +1452,45 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
         }
         return rc;
     }
-    HIPCHK(c, launch_embed(c->spec(s0), bins, bits, c->ph_jit, ep, g, c->err, st));
+    HIPCHK(c, launch_embed(c->spec(s0), bins, bits, jit, ep, g, c->err, st));
     return enqueue_inverse(c, s0, g, rgb_out, st);
 }
 static int extract_chunk(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, const tfft_bin* bins, uint64_t n_bits,
-                         double alpha, uint8_t* bits_out, hipStream_t st) {
+                         double alpha, uint8_t* bits_out, hipStream_t st, const WalkSrc* walks = nullptr) {
     const Slot& s = c->slots[s0];
     if (!index_ok(c, n_bits) || !phase_ok(c, n_bits)) return TFFT_E_STATE;
+    if (walks && (c->bit_index || c->ph_jit)) return TFFT_E_STATE;
+    const bool adaptive = walks ? walks->adaptive != 0 : c->ph_adaptive != 0;
+    const float* jit = walks ? walks->jit : c->ph_jit;
     // adaptive alpha with |alpha| < pi/2: a = alpha*clamp(.., 0.5, 2) keeps the sign of alpha and |a| < pi, so the targets j +- a are
     // symmetric about j and j + pi and the bit is the side of that line -- what the fixed-alpha read decides.
     // Beyond, the decision depends on the medians: the single-image calls cover that case
-    if (c->ph_adaptive && !(fabs(alpha) < M_PI / 2)) return TFFT_E_INVALID;
+    if (adaptive && !(fabs(alpha) < M_PI / 2)) return TFFT_E_INVALID;
     const int which = (c->stream2 && st == c->stream2) ? 1 : 0;
-    EmbedParams ep = embed_params(c, s, n_bits, alpha, 0, nullptr, c->ph_jit != nullptr);
+    EmbedParams ep = embed_params(c, s, n_bits, alpha, 0, nullptr, jit != nullptr);
+    if (walks) ep.bins_stride = n_bits;
     int rc;
     // (the bucket build is per call: it pays off from about 8 images per chunk; TFFT_TILE_READ=2/3 force it)
     // a registered list keeps its buckets (no per-call build to pay for): then the tile-resident read also serves small chunks of LARGE
     // images (one 4K image: 0.739 -> 0.725 ms per round trip; one 1080p image has too few tiles to fill the chip: 0.265 -> 0.301)
-    const bool reg_large = bins == c->reg_bins && n_bits == c->reg_n && (unsigned long long)s.PH * s.PWi >= (1ull << 23);
+    const bool reg_large = !walks && bins == c->reg_bins && n_bits == c->reg_n && (unsigned long long)s.PH * s.PWi >= (1ull << 23);
     // (an alpha outside (0, pi) takes the general phase comparison of k_read: the tile kernel reads the sign of Im only)
     if (c->tile_read && n_bits > 0 && alpha > 0.0 && alpha < M_PI && (g >= 8 || c->tile_read >= 2 || reg_large)) {
         // The spectrum is only ever read at the bins of the list: bucket them by column tile and let the final
         // forward column step read the bits out of its LDS-resident tiles -- no spectrum store, no k_read.
         const ColPlan pl = plan_cols(c, s.PH, s.PWi, g);
         const int G = pl.direct ? 1 : (1 << pl.log_n1), ntiles = (s.PWi / 2 + 15) / 16, nb = 3 * ntiles * G;
-        rc = ensure_buckets(c, which, n_bits, nb);
+        rc = walks ? TFFT_OK : ensure_buckets(c, which, n_bits, nb);
         if (rc) return rc;
         auto& tb = c->tb[which];
         HIPCHK(c, hipMemsetAsync(bits_out, 0, (size_t)g * n_bits, st));          // bins the walk would never produce read as 0 (k_read does the same)
-        rc = build_buckets(c, which, bins, n_bits, s, G, st);
+        rc = walks ? build_buckets_walks(c, which, bins, n_bits, g, s, G, jit, st) : build_buckets(c, which, bins, n_bits, s, G, st);
         if (rc) return rc;
-        rc = gather_jitter(c, which, n_bits, nb, st);
+        if (!walks) rc = gather_jitter(c, which, n_bits, nb, st);
         if (rc) return rc;
         ColParams rd{};
         rd.rd_bins = tb.ent; rd.rd_off = tb.off; rd.rd_bits = bits_out; rd.rd_n = n_bits; rd.trash = c->trash;
-        rd.em_jp = c->ph_jit ? tb.jp : nullptr;
+        rd.em_jp = jit ? tb.jp : nullptr; rd.rd_walks = walks ? 1 : 0;
         StageMode md;
         md.fwd_read = &rd;
         rc = enqueue_forward(c, s0, g, rgb_in, st, md);
@@ -1462,16 +1499,17 @@ static int extract_chunk(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, cons
         // the spectrum is only read at the bins of the list: rows above the highest one are never stored
         int* last_row = c->last_row + which;
         auto& tbr = c->tb[which];
-        const bool registered = bins == c->reg_bins && n_bits == c->reg_n;
+        const bool registered = !walks && bins == c->reg_bins && n_bits == c->reg_n;
         if (!(registered && tbr.row_for == bins && tbr.row_n == n_bits && tbr.row_ph == s.PH && tbr.row_pw == s.PWi)) {
-            HIPCHK(c, launch_bins_last_row(bins, n_bits, s.PH, s.PWi, last_row, st));
+            // (one walk per image: the highest row over all the chunk's lists)
+            HIPCHK(c, launch_bins_last_row(bins, walks ? (uint64_t)g * n_bits : n_bits, s.PH, s.PWi, last_row, st));
             tbr.row_for = registered ? bins : nullptr; tbr.row_n = n_bits; tbr.row_ph = s.PH; tbr.row_pw = s.PWi;
         }
         StageMode md;
         md.fwd_last_row = last_row;
         rc = enqueue_forward(c, s0, g, rgb_in, st, md);
         if (rc) return rc;
-        HIPCHK(c, launch_read(c->spec(s0), bins, c->ph_jit, ep, g, bits_out, c->err, st));
+        HIPCHK(c, launch_read(c->spec(s0), bins, jit, ep, g, bits_out, c->err, st));
     }
     for (int i = 0; i < g; i++) c->slots[s0 + i].has_spec = false;      // partial or no spectrum: not for tfft_medians & co
     return TFFT_OK;
@@ -1711,9 +1749,12 @@ static int ensure_stream_io(tfft_ctx* c, uint64_t plen) {
     return TFFT_OK;
 }
 
+// walks != nullptr: `bins` holds one list of n_bits per image (and walks->jit, a host array, its jitter or nullptr); both travel per part
+// of the ring with the images, to the part's share of the staging lists
 static int batch_host(tfft_ctx* c, bool embed, int n_images, const uint8_t* rgb, int w, int h, int center,
                       const tfft_bin* bins, const uint8_t* bits, uint64_t n_bits, double alpha, double rmin, double rmax,
-                      double magmin, uint64_t* usable, uint8_t* rgb_out, uint8_t* bits_out, const StreamIO* sio = nullptr) {
+                      double magmin, uint64_t* usable, uint8_t* rgb_out, uint8_t* bits_out, const StreamIO* sio = nullptr,
+                      const WalkSrc* walks = nullptr) {
     if (n_images == 0) return TFFT_OK;
     int rc = pipe_init(c);
     if (rc) return rc;
@@ -1731,7 +1772,7 @@ static int batch_host(tfft_ctx* c, bool embed, int n_images, const uint8_t* rgb,
     // the slots form a ring of up to four parts: copy-in of part k+1..k+3 overlaps the kernels of part k
     const int nhalves = c->n_slots >= 8 ? 4 : (c->n_slots >= 2 ? 2 : 1);
     const int half = c->n_slots / nhalves;
-    HIPCHK(c, hipMemcpyAsync(c->stage_bins, bins, n_bits * sizeof(tfft_bin), hipMemcpyHostToDevice, c->stream));
+    if (!walks) HIPCHK(c, hipMemcpyAsync(c->stage_bins, bins, n_bits * sizeof(tfft_bin), hipMemcpyHostToDevice, c->stream));
     int chunk = 0;
     for (int i0 = 0; i0 < n_images; i0 += half, chunk++) {
         const int g = (n_images - i0 < half) ? n_images - i0 : half;
@@ -1742,6 +1783,13 @@ static int batch_host(tfft_ctx* c, bool embed, int n_images, const uint8_t* rgb,
         HIPCHK(c, hipStreamWaitEvent(c->s_in, c->ev_comp[hh], 0));
         // the pipeline treats the half's staging area as one packed batch buffer (g images back to back)
         HIPCHK(c, hipMemcpyAsync(c->img(s0), rgb + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, c->s_in));
+        tfft_bin* d_bins = (tfft_bin*)c->stage_bins + (walks ? (size_t)s0 * n_bits : 0);
+        float* d_jit = (float*)c->stage_jit + (size_t)s0 * n_bits;
+        if (walks) {
+            HIPCHK(c, hipMemcpyAsync(d_bins, bins + (size_t)i0 * n_bits, (size_t)g * n_bits * sizeof(tfft_bin), hipMemcpyHostToDevice, c->s_in));
+            if (walks->jit) HIPCHK(c, hipMemcpyAsync(d_jit, walks->jit + (size_t)i0 * n_bits, (size_t)g * n_bits * sizeof(float), hipMemcpyHostToDevice, c->s_in));
+        }
+        const WalkSrc wpart{walks && walks->jit ? d_jit : nullptr, walks ? walks->adaptive : 0};
         if (embed && !sio) HIPCHK(c, hipMemcpyAsync(d_bits, bits + (size_t)i0 * n_bits, (size_t)g * n_bits, hipMemcpyHostToDevice, c->s_in));
         if (embed && sio) {      // 38 + plen bytes per image instead of 912 + 56*plen
             HIPCHK(c, hipMemcpyAsync(c->sio_hdr + (size_t)s0 * 38, sio->header_in + (size_t)i0 * 38, (size_t)g * 38, hipMemcpyHostToDevice, c->s_in));
@@ -1758,10 +1806,11 @@ static int batch_host(tfft_ctx* c, bool embed, int n_images, const uint8_t* rgb,
             fr = FrameSrc{c->sio_hdr + (size_t)s0 * 38, c->sio_pay + (size_t)s0 * sio->plen, sio->plen};
         }
         if (embed)
-            rc = embed_chunk(c, s0, g, c->img(s0), (const tfft_bin*)c->stage_bins, sio ? nullptr : d_bits, n_bits, alpha, rmin, rmax, magmin,
-                             usable ? c->usable + s0 : nullptr, c->out_pool + (size_t)s0 * c->img_stride_b, c->stream, limit, sio ? &fr : nullptr);   // packed, like the input
+            rc = embed_chunk(c, s0, g, c->img(s0), d_bins, sio ? nullptr : d_bits, n_bits, alpha, rmin, rmax, magmin,
+                             usable ? c->usable + s0 : nullptr, c->out_pool + (size_t)s0 * c->img_stride_b, c->stream, limit, sio ? &fr : nullptr,
+                             walks ? &wpart : nullptr);   // packed, like the input
         else
-            rc = extract_chunk(c, s0, g, c->img(s0), (const tfft_bin*)c->stage_bins, n_bits, alpha, d_bout, c->stream);
+            rc = extract_chunk(c, s0, g, c->img(s0), d_bins, n_bits, alpha, d_bout, c->stream, walks ? &wpart : nullptr);
         if (rc) return rc;
         if (!embed && sio)       // header -> clen -> payload on the device: only packed bytes and a status word go back
             HIPCHK(c, launch_stream_decode(d_bout, n_bits, sio->max_plen, g, c->sio_hdr + (size_t)s0 * 38, c->sio_pay + (size_t)s0 * sio->max_plen,
@@ -1812,6 +1861,124 @@ int tfft_extract_stream_batch(tfft_ctx* c, int n_images, const uint8_t* rgb, int
     StreamIO io; io.header_out = header_out; io.payload_out = payload_out; io.max_plen = max_payload_len; io.status_out = status_out;
     return batch_host(c, false, n_images, rgb, w, h, center, bins, nullptr, n_bins, alpha, 0, 0, 0, nullptr, nullptr, raw_bits_out, &io);
 }
+// ---------------------------------------------------------------- one walk per image (own keys, cover-dependent paths)
+// The shared-list pipelines above with the lists, jitter and adaptive alpha per image: the buckets are built for the chunk's own lists on
+// every call (launch_bucket_walks), the column kernels find image i's buckets at a per-image base (k_fft_cols<..., PI>).  No cached
+// sequence (TFFT_GRAPHS) is captured or replayed, and the shared-list state of the context (bit index, phase-option jitter) is refused.
+static int walks_args_ok(const tfft_ctx* c, int n_images, uint64_t n_bins, double alpha, int adaptive, bool extract) {
+    if (!c || n_images < 0 || n_bins == 0) return TFFT_E_INVALID;
+    if (c->bit_index || c->ph_jit) return TFFT_E_STATE;
+    if (extract && adaptive && !(fabs(alpha) < M_PI / 2)) return TFFT_E_INVALID;      // (see extract_chunk)
+    if ((uint64_t)c->n_slots * n_bins > 0xFFFFFFFFull) return TFFT_E_TOO_LARGE;      // a chunk's entries are addressed with 32 bits
+    return TFFT_OK;
+}
+
+int tfft_embed_stream_batch_walks_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, const void* bins_dev,
+                                      const void* jitter_dev, uint64_t n_bins, int adaptive, const void* header_dev, const void* payload_dev,
+                                      uint64_t payload_len, double alpha, double rmin, double rmax, double magmin, void* usable_out_dev,
+                                      void* rgb_out_dev) {
+    if (!c || !rgb_dev || !rgb_out_dev || !bins_dev || !header_dev || (payload_len && !payload_dev)) return TFFT_E_INVALID;
+    int rc = walks_args_ok(c, n_images, n_bins, alpha, adaptive, false);
+    if (rc) return rc;
+    if (n_bins < 912 || payload_len > (n_bins - 912) / 56) return TFFT_E_INVALID;      // (before the multiplication: a huge length must not wrap)
+    const uint64_t n_bits = 38ull * 24 + payload_len * 56;           // S:986-995
+    const size_t img_bytes = (size_t)w * h * 3;
+    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
+        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+        rc = batch_geometry(c, g, w, h, center);
+        if (rc) return rc;
+        int h1 = 0;
+        rc = split_fork(c, g, &h1);
+        if (rc) return rc;
+        for (int part = 0; part < (h1 ? 2 : 1); part++) {
+            const int s0 = part ? h1 : 0, gp = h1 ? (part ? g - h1 : h1) : g, i1 = i0 + s0;
+            const FrameSrc fr{(const uint8_t*)header_dev + (size_t)i1 * 38, (const uint8_t*)payload_dev + (size_t)i1 * payload_len, payload_len};
+            const WalkSrc ws{jitter_dev ? (const float*)jitter_dev + (size_t)i1 * n_bins : nullptr, adaptive ? 1 : 0};
+            rc = embed_chunk(c, s0, gp, (const uint8_t*)rgb_dev + (size_t)i1 * img_bytes, (const tfft_bin*)bins_dev + (size_t)i1 * n_bins, nullptr,
+                             n_bins, alpha, rmin, rmax, magmin, usable_out_dev ? (unsigned long long*)usable_out_dev + i1 : nullptr,
+                             (uint8_t*)rgb_out_dev + (size_t)i1 * img_bytes, part ? c->stream2 : c->stream, n_bits, &fr, &ws);
+            if (rc) return rc;
+        }
+        if (h1) { rc = split_join(c); if (rc) return rc; }
+    }
+    return n_images ? check_err_flag(c) : TFFT_OK;
+}
+
+int tfft_extract_stream_batch_walks_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, const void* bins_dev,
+                                        const void* jitter_dev, uint64_t n_bins, int adaptive, double alpha, void* header_out_dev,
+                                        void* payload_out_dev, uint64_t max_payload_len, void* status_out_dev, void* raw_bits_out_dev) {
+    if (!c || !rgb_dev || !bins_dev || !header_out_dev || !status_out_dev || (max_payload_len && !payload_out_dev)) return TFFT_E_INVALID;
+    int rc = walks_args_ok(c, n_images, n_bins, alpha, adaptive, true);
+    if (rc) return rc;
+    if (!raw_bits_out_dev) { rc = ensure_stream(c, n_bins); if (rc) return rc; }
+    else if (!c->stream_plen && dev_alloc(c, (void**)&c->stream_plen, (size_t)c->n_slots * sizeof(unsigned))) return TFFT_E_NOMEM;
+    const size_t img_bytes = (size_t)w * h * 3;
+    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
+        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+        rc = batch_geometry(c, g, w, h, center);
+        if (rc) return rc;
+        int h1 = 0;
+        rc = split_fork(c, g, &h1);
+        if (rc) return rc;
+        for (int part = 0; part < (h1 ? 2 : 1); part++) {
+            const int s0 = part ? h1 : 0, gp = h1 ? (part ? g - h1 : h1) : g, i1 = i0 + s0;
+            hipStream_t st = part ? c->stream2 : c->stream;
+            // every position of the image's own walk is read in the pass that has the spectrum on chip, then the header decides (S:1223-1264)
+            uint8_t* raw = raw_bits_out_dev ? (uint8_t*)raw_bits_out_dev + (size_t)i1 * n_bins : c->stream_bits + (size_t)s0 * n_bins;
+            const WalkSrc ws{jitter_dev ? (const float*)jitter_dev + (size_t)i1 * n_bins : nullptr, adaptive ? 1 : 0};
+            rc = extract_chunk(c, s0, gp, (const uint8_t*)rgb_dev + (size_t)i1 * img_bytes, (const tfft_bin*)bins_dev + (size_t)i1 * n_bins, n_bins, alpha,
+                               raw, st, &ws);
+            if (rc) return rc;
+            HIPCHK(c, launch_stream_decode(raw, n_bins, max_payload_len, gp, (uint8_t*)header_out_dev + (size_t)i1 * 38,
+                                           (uint8_t*)payload_out_dev + (size_t)i1 * max_payload_len, (int*)status_out_dev + i1, c->stream_plen + s0, st));
+        }
+        if (h1) { rc = split_join(c); if (rc) return rc; }
+    }
+    return n_images ? check_err_flag(c) : TFFT_OK;
+}
+
+int tfft_embed_stream_batch_walks(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int h, int center, const tfft_bin* bins, const float* jitter,
+                                  uint64_t n_bins, int adaptive, const uint8_t* header, const uint8_t* payload, uint64_t payload_len, double alpha,
+                                  double rmin, double rmax, double magmin, uint64_t* usable_out, uint8_t* rgb_out) {
+    if (!c || !rgb || !rgb_out || !bins || !header || (payload_len && !payload)) return TFFT_E_INVALID;
+    int rc = walks_args_ok(c, n_images, n_bins, alpha, adaptive, false);
+    if (rc) return rc;
+    if (n_bins < 912 || payload_len > (n_bins - 912) / 56) return TFFT_E_INVALID;
+    StreamIO io; io.header_in = header; io.payload_in = payload; io.plen = payload_len;
+    const WalkSrc ws{jitter, adaptive ? 1 : 0};
+    return batch_host(c, true, n_images, rgb, w, h, center, bins, nullptr, n_bins, alpha, rmin, rmax, magmin, usable_out, rgb_out, nullptr, &io, &ws);
+}
+int tfft_extract_stream_batch_walks(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int h, int center, const tfft_bin* bins, const float* jitter,
+                                    uint64_t n_bins, int adaptive, double alpha, uint8_t* header_out, uint8_t* payload_out, uint64_t max_payload_len,
+                                    int32_t* status_out, uint8_t* raw_bits_out) {
+    if (!c || !rgb || !bins || !header_out || !status_out || (max_payload_len && !payload_out)) return TFFT_E_INVALID;
+    int rc = walks_args_ok(c, n_images, n_bins, alpha, adaptive, true);
+    if (rc) return rc;
+    StreamIO io; io.header_out = header_out; io.payload_out = payload_out; io.max_plen = max_payload_len; io.status_out = status_out;
+    const WalkSrc ws{jitter, adaptive ? 1 : 0};
+    return batch_host(c, false, n_images, rgb, w, h, center, bins, nullptr, n_bins, alpha, 0, 0, 0, nullptr, nullptr, raw_bits_out, &io, &ws);
+}
+
+int tfft_lowfreq_mag_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, int region, void* out_dev) {
+    if (!c || n_images < 0 || !rgb_dev || !out_dev || region < 1 || region > 8) return TFFT_E_INVALID;
+    if (n_images == 0) return TFFT_OK;
+    Slot s;
+    int rc = set_geometry(c, s, w, h, center);
+    if (rc) return rc;
+    if (region > s.PH || region > s.PW) return TFFT_E_INVALID;
+    // the row sums of image k of a chunk in tmp(k), as tfft_lowfreq_mag keeps them (free outside a call: nothing lives there between calls)
+    const size_t row_bytes = (size_t)s.H * 3 * region * sizeof(double2), out_len = (size_t)3 * region * region;
+    if (row_bytes > c->slot_stride * sizeof(float2)) return TFFT_E_INVALID;
+    const size_t img_bytes = (size_t)w * h * 3;
+    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
+        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+        HIPCHK(c, launch_lowfreq_f64_batch((const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, s.W, s.H, s.PW, s.PH, s.center, region, g,
+                                           (double2*)c->tmp(0), c->slot_stride * sizeof(float2) / sizeof(double2), (double*)out_dev + (size_t)i0 * out_len,
+                                           c->stream));
+    }
+    return TFFT_OK;
+}
+
 void* tfft_host_alloc(size_t bytes) {
     void* p = nullptr;
     return hipHostMalloc(&p, bytes, 0) == hipSuccess ? p : nullptr;

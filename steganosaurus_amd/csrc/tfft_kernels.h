@@ -45,7 +45,7 @@ struct ColParams {
     int em_m2;                       // COLS_EMIT: store |F|^2 (float, `out` reinterpreted, same byte offset per image) instead of the complex
                                      // spectrum, the packed column 0 to st_col0: all the statistics read (launch_medians col0_m2)
     const uint8_t* em_pb;            // COLS_EMBED: em_n stream bits per image in the same order (k_gather_bits; 2 = not written)
-    uint64_t em_n;                   // list stride between images (the length of the bin list)
+    uint64_t em_n;                   // list stride between images (the length of the bin list; 0 with rd_walks, whose entry indices are absolute)
     float em_cos, em_sin;
     // phase options of the batched calls (tfft_set_phase_options); COLS_EMBED and COLS_READ only
     const float2* em_jp;             // jitter as unit phasors (cos j, sin j), indexed like rd_bins (shared by all images); nullptr = no jitter
@@ -82,6 +82,7 @@ struct ColParams {
     int tiles_per_block;  // adjacent 16-column tiles walked by one workgroup
     size_t plane_stride;  // float2 elements between planes (PH*M)
     size_t img_stride;    // float2 elements between images (grid.z = 3*n_images)
+    int rd_walks;         // the bucket modes with one walk per image (launch_bucket_walks layout, k_fft_cols<..., PI = true>); 0 = one shared list
 };
 
 struct EmbedParams {
@@ -98,6 +99,7 @@ struct EmbedParams {
     // embed only, stream pipelines: the bits come straight out of the packed frame (38-byte header, frame_plen payload bytes per image)
     const uint8_t* frame_hdr; const uint8_t* frame_pay; uint64_t frame_plen;
     const float* med_dev;        // adaptive, batched calls: 3 medians per image on the device (image i at med_dev + 3*i) instead of med[]
+    uint64_t bins_stride;        // one walk per image: image i's bins (and jitter) at bins + i*bins_stride; 0 = one list shared by every image
 };
 
 struct CapParams {
@@ -180,6 +182,16 @@ hipError_t audit_load_rgb8_f64(const uint8_t* rgb_dev, int W, int H, int PW, int
 // bucket the bin list by (plane, 16-column tile, row group y % G) for the tile-resident read: counts -> offsets -> entries
 hipError_t launch_bucket_bins(const tfft_bin* bins, const uint32_t* bit_index, uint64_t n, int PH, int PW, int G,
                               unsigned* cnt, unsigned* off, TileBin* out, int* err, int force_global, hipStream_t s);
+// one walk per image: n_images lists of n bins (image i's at bins + i*n, no bit index) bucketed by (image, plane, group, column tile).
+// Image i owns buckets [i*nb, (i+1)*nb), nb = 3*ntiles*G, and bucket n_images*nb holds the invalid bins of all (the error flag is
+// raised for those), so that image i's entries are exactly [i*n, (i+1)*n) for valid lists; TileBin::bit = the position in the image's own
+// list.  cnt / off hold n_images*nb + 2 words (+ the scan's block totals)
+hipError_t launch_bucket_walks(const tfft_bin* bins, uint64_t n, int n_images, int PH, int PW, int G, unsigned* cnt, unsigned* off, TileBin* out,
+                               int* err, hipStream_t s);
+// ... and the stream bits / the jitter phasors of those entries (entry e belongs to image e / n; bits and jitter at image*n + bit)
+hipError_t launch_gather_bits_walks(const TileBin* ent, const uint8_t* bits, const uint8_t* hdr, const uint8_t* pay, uint64_t plen, uint64_t n,
+                                    uint64_t limit, int n_images, uint8_t* out, hipStream_t s);
+hipError_t launch_gather_jitter_walks(const TileBin* ent, const float* jitter, uint64_t n, int n_images, float2* out, hipStream_t s);
 // highest stored row any bin of the list touches -> *last_row (device int, reset here)
 hipError_t launch_stat_guess(const float2* mini, int PH, int PW, int Ms, size_t mini_img_stride, int n_images, SelectState* st, const struct CapParams* cap,
                              unsigned* partial, int col0_packed, hipStream_t s);
@@ -215,5 +227,9 @@ hipError_t launch_export_full(const float2* spec, int PH, int PW, int PWout, flo
 // compute_cover_hash's low-frequency magnitudes in fp64 from the pixels (rowsum: H*3*region double2 of scratch)
 hipError_t launch_lowfreq_f64(const uint8_t* rgb, int W, int H, int PW, int PH, int center, int region, double2* rowsum, double* out,
                               hipStream_t s);
+// ... for n_images images of a batch (W*H*3 bytes apart): rowsum of image i at rowsum + i*rowsum_stride (double2), out at out + i*3*region^2;
+// the same summation order as the single image, bit for bit
+hipError_t launch_lowfreq_f64_batch(const uint8_t* rgb, int W, int H, int PW, int PH, int center, int region, int n_images, double2* rowsum,
+                                    size_t rowsum_stride, double* out, hipStream_t s);
 
 }  // namespace tfft

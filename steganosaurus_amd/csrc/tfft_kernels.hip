@@ -904,7 +904,12 @@ __device__ __forceinline__ unsigned frame_bit(const uint8_t* __restrict__ header
 //       tile that follows then also waits for the stores just issued (their whole latency, every tile).  The launcher picks it.
 // PH: the phase options of the batched calls (ColParams::em_jp / em_med, tfft_set_phase_options) are compiled in -- COLS_EMBED and
 //     COLS_READ only, their own instantiations, so that the fixed-alpha kernels stay exactly as they are (registers, occupancy)
-template <int LOGL, int SIGN, int MODE = COLS_PLAIN, bool DC = false, bool TW = false, bool FULL = false, bool PH = false>
+// PI: one walk per image (tfft_*_stream_batch_walks_dev, launch_bucket_walks): image i's buckets follow image i-1's (bucket
+//     ((3*i + plane)*G + g)*ntiles + tile) and hold ABSOLUTE entry indices (image i's entries at [i*n, (i+1)*n)), so em_fl / em_pb /
+//     em_jp are indexed by the entry alone: the launcher passes em_n = 0.  (Written as `PI ? 0 : img*em_n` here instead, the COLS_STAT
+//     step of a 1080p launch spilled a register.)
+//     Bucket modes only, their own instantiations: the shared-list kernels keep their registers and occupancy
+template <int LOGL, int SIGN, int MODE = COLS_PLAIN, bool DC = false, bool TW = false, bool FULL = false, bool PH = false, bool PI = false>
 __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE == COLS_EMIT && TFFT_COLS_PFEMIT) ? 1 : (FULL ? TFFT_COLS_WAVES(LOGL) : imin(2, TFFT_COLS_WAVES(LOGL)))) k_fft_cols(const float2* in, float2* out, const float2* __restrict__ tw,
                            ColParams P) {
     constexpr int L = 1 << LOGL, E = elems_for(L), T = L / E, C = 16;
@@ -1049,7 +1054,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
     // and without the branch trees a register array indexed by the tile turned into
     unsigned* lds_eo = reinterpret_cast<unsigned*>(lds_tw + (TWL ? L : 0) + blockDim.z * C) + gl * (NOFF + 2);
     if (MODE == COLS_READ || MODE == COLS_EMBED || MODE == COLS_EMIT || MODE == COLS_STAT) {
-        const unsigned b0 = (unsigned)((plane * P.G + (g < P.G ? g : 0)) * ntiles);
+        const unsigned b0 = (unsigned)(((PI ? (int)blockIdx.z : plane) * P.G + (g < P.G ? g : 0)) * ntiles);      // (PI: blockIdx.z = 3*img + plane)
         for (int i = em_tid; i <= NOFF; i += em_nthr) lds_eo[i] = P.rd_off[b0 + (unsigned)imin(tile0 + i, ntiles)];
     }
     unsigned* lds_hist = reinterpret_cast<unsigned*>(tfft_smem + P.hist_lds_off);
@@ -1552,9 +1557,11 @@ __global__ void k_embed(float2* __restrict__ spec, const tfft_bin* __restrict__ 
                         const float* __restrict__ jitter, EmbedParams P, int* __restrict__ err) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P.n) return;
-    const int img = blockIdx.y;              // images of a batch share the bin list, not the bits
+    const int img = blockIdx.y;              // images of a batch share the bin list, not the bits (unless each has its own walk: bins_stride)
     spec += (size_t)img * P.img_stride;
     if (bits) bits += (size_t)img * P.n;
+    bins += (size_t)img * P.bins_stride;
+    if (jitter) jitter += (size_t)img * P.bins_stride;
     const tfft_bin bn = bins[i];
     const uint64_t j = P.bit_index ? (uint64_t)P.bit_index[i] : i;      // the stream bit this bin carries
     if (j >= P.limit) return;                // the stream ends before this position of the walk (tfft_embed_stream_batch_dev)
@@ -1631,6 +1638,8 @@ __global__ void k_read(const float2* __restrict__ spec, const tfft_bin* __restri
     const int img = blockIdx.y;
     spec += (size_t)img * P.img_stride;
     bits_out += (size_t)img * P.n;
+    bins += (size_t)img * P.bins_stride;
+    if (jitter) jitter += (size_t)img * P.bins_stride;
     const tfft_bin bn = bins[i];
     const uint64_t j = P.bit_index ? (uint64_t)P.bit_index[i] : i;
     const int x = bn.x, y = bn.y, p = bn.plane;
@@ -1776,6 +1785,86 @@ __global__ void k_bucket_fill(const tfft_bin* __restrict__ bins, const uint32_t*
         const unsigned pos = local ? atomicAdd(&lc[b - bmin], 1u) : off[b] + atomicAdd(&cursor[b], 1u);
         out[pos] = tb;
     }
+}
+
+// One walk per image (launch_bucket_walks): image i's list is bins[i*n .. (i+1)*n) and owns buckets [i*nb, (i+1)*nb); one more bucket at
+// n_images*nb collects the invalid bins of every image (the error flag is raised for them), so that after the scan image i's entries fill
+// exactly [i*n, (i+1)*n) whenever its list is valid.  A workgroup takes a contiguous chunk of ONE image's list (a walk scatters its bins over
+// the whole grid: no narrow span to count in, as the shared list in address order has) and counts it in an LDS histogram of the image's
+// buckets (+ the invalid one) when they fit, touching each global counter once per chunk; otherwise it adds to the global counters directly.
+__global__ void k_bucket_count_walks(const tfft_bin* __restrict__ bins, uint64_t n, int chunks, int PH, int PW, int G, unsigned nb,
+                                     unsigned* __restrict__ cnt, int* __restrict__ err) {
+    unsigned* lc = reinterpret_cast<unsigned*>(tfft_smem);        // [nb + 1] when it fits BUCKET_LCAP
+    const int img = blockIdx.x / chunks, ch = blockIdx.x - img * chunks, nimg = gridDim.x / chunks;
+    const uint64_t per = (n + chunks - 1) / chunks, lo = (uint64_t)ch * per, hi = (lo + per < n) ? lo + per : n;
+    const bool local = nb + 1 <= BUCKET_LCAP;
+    const tfft_bin* b0 = bins + (size_t)img * n;
+    unsigned* gc = cnt + (size_t)img * nb;
+    unsigned* gbad = cnt + (size_t)nimg * nb;
+    if (local) {
+        for (unsigned i = threadIdx.x; i <= nb; i += blockDim.x) lc[i] = 0;
+        __syncthreads();
+    }
+    for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+        unsigned b; TileBin tb;
+        if (!tile_bin_of(b0[i], PH, PW, G, b, tb)) { atomicOr(err, 1); b = nb; }
+        atomicAdd(local ? &lc[b] : (b < nb ? &gc[b] : gbad), 1u);
+    }
+    if (local) {
+        __syncthreads();
+        for (unsigned i = threadIdx.x; i <= nb; i += blockDim.x) if (lc[i]) atomicAdd(i < nb ? &gc[i] : gbad, lc[i]);
+    }
+}
+__global__ void k_bucket_fill_walks(const tfft_bin* __restrict__ bins, uint64_t n, int chunks, int PH, int PW, int G, unsigned nb,
+                                    unsigned* __restrict__ cursor, const unsigned* __restrict__ off, TileBin* __restrict__ out) {
+    unsigned* lc = reinterpret_cast<unsigned*>(tfft_smem);
+    const int img = blockIdx.x / chunks, ch = blockIdx.x - img * chunks, nimg = gridDim.x / chunks;
+    const uint64_t per = (n + chunks - 1) / chunks, lo = (uint64_t)ch * per, hi = (lo + per < n) ? lo + per : n;
+    const bool local = nb + 1 <= BUCKET_LCAP;
+    const tfft_bin* b0 = bins + (size_t)img * n;
+    auto gidx = [&](unsigned b) -> size_t { return b < nb ? (size_t)img * nb + b : (size_t)nimg * nb; };
+    if (local) {
+        for (unsigned i = threadIdx.x; i <= nb; i += blockDim.x) lc[i] = 0;
+        __syncthreads();
+        for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+            unsigned b; TileBin tb;
+            if (!tile_bin_of(b0[i], PH, PW, G, b, tb)) b = nb;
+            atomicAdd(&lc[b], 1u);
+        }
+        __syncthreads();
+        for (unsigned i = threadIdx.x; i <= nb; i += blockDim.x) {
+            const unsigned k = lc[i];
+            if (k) lc[i] = off[gidx(i)] + atomicAdd(&cursor[gidx(i)], k);      // start of this workgroup's range in the bucket
+        }
+        __syncthreads();
+    }
+    for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+        unsigned b; TileBin tb;
+        if (!tile_bin_of(b0[i], PH, PW, G, b, tb)) { b = nb; tb.k = 0; tb.c = 0; tb.conj = 0; }
+        tb.bit = (uint32_t)i;
+        const unsigned pos = local ? atomicAdd(&lc[b], 1u) : off[gidx(b)] + atomicAdd(&cursor[gidx(b)], 1u);
+        out[pos] = tb;
+    }
+}
+// the stream bits of the per-image entries: entry e is image e / n's (launch_bucket_walks), out[e] as k_gather_bits writes out[img*n + e]
+__global__ void k_gather_bits_walks(const TileBin* __restrict__ ent, const uint8_t* __restrict__ bits, const uint8_t* __restrict__ hdr,
+                                    const uint8_t* __restrict__ pay, uint64_t plen, uint64_t n, uint64_t limit, uint64_t total,
+                                    uint8_t* __restrict__ out) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const uint64_t img = e / n;
+    const uint64_t j = ent[e].bit;
+    unsigned b = 2u;
+    if (j < limit) b = hdr ? frame_bit(hdr + img * 38, pay + img * plen, j) : (unsigned)(bits[img * n + j] & 1u);
+    out[e] = (uint8_t)b;
+}
+__global__ void k_gather_jitter_walks(const TileBin* __restrict__ ent, const float* __restrict__ jitter, uint64_t n, uint64_t total,
+                                      float2* __restrict__ out) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const uint64_t j = ent[e].bit;
+    const double jt = j < n ? (double)jitter[(e / n) * n + j] : 0.0;
+    out[e] = make_float2((float)cos(jt), (float)sin(jt));
 }
 
 // ---------------------------------------------------------------------------
@@ -2494,15 +2583,19 @@ __global__ void k_export_full(const float2* __restrict__ spec, int PH, int PW, i
 // 3 x region x region corner of the spectrum, i.e. 192 inner products with the image -- no transform needed, and fp64
 // keeps the quantiser floor(log(1+mag)/2) (S:433) on the reference's side of every bucket edge (the fp32 spectrum is
 // 1e-7..1e-6 off; these values agree with the reference's fp64 FFT to ~1e-13).
-//   rows: grid (H)  block (32, region)   rowsum[n][p][x] = sum_m s(m) pix[n][m][p] exp(+2 pi i x m/PW)
-//   cols: grid (3*region*region)  block 256   out[p][y][x] = | sum_n s(n) rowsum[n][p][x] exp(+2 pi i y n/PH) |
+//   rows: grid (H, images)  block (32, region)   rowsum[n][p][x] = sum_m s(m) pix[n][m][p] exp(+2 pi i x m/PW)
+//   cols: grid (3*region*region, images)  block 256   out[p][y][x] = | sum_n s(n) rowsum[n][p][x] exp(+2 pi i y n/PH) |
+//   (image i of a batch: pixels W*H*3 bytes on, rowsum rs_stride double2 on, out 3*region^2 on; the sums run in the same order)
 __device__ __forceinline__ void unit_2pi(long long k, int N, double& c, double& s) {      // exp(2 pi i k/N), N a power of two
     const double t = (double)(k & (long long)(N - 1)) / (double)N;                            // exact
     sincos(6.283185307179586476925286766559 * t, &s, &c);
 }
-__global__ void k_lowfreq_rows_f64(const uint8_t* __restrict__ rgb, int W, int PW, int center, int region, double2* __restrict__ rowsum) {
+__global__ void k_lowfreq_rows_f64(const uint8_t* __restrict__ rgb, int W, int PW, int center, int region, double2* __restrict__ rowsum,
+                                   size_t img_bytes, size_t rs_stride) {
     double* red = reinterpret_cast<double*>(tfft_smem);                 // [region][32][6]
     const int lane = threadIdx.x, x = threadIdx.y, n = blockIdx.x;
+    rgb += (size_t)blockIdx.y * img_bytes;
+    rowsum += (size_t)blockIdx.y * rs_stride;
     const uint8_t* row = rgb + (size_t)n * W * 3;
     double acc[6] = {0, 0, 0, 0, 0, 0};
     for (int m = lane; m < W; m += 32) {
@@ -2525,9 +2618,12 @@ __global__ void k_lowfreq_rows_f64(const uint8_t* __restrict__ rgb, int W, int P
     const double* tot = red + (size_t)x * 32 * 6;                        // lane 0's slot holds the sums of this x
     if (lane < 3) rowsum[((size_t)n * 3 + lane) * region + x] = make_double2(tot[2 * lane], tot[2 * lane + 1]);
 }
-__global__ void k_lowfreq_cols_f64(const double2* __restrict__ rowsum, int H, int PH, int center, int region, double* __restrict__ out) {
+__global__ void k_lowfreq_cols_f64(const double2* __restrict__ rowsum, int H, int PH, int center, int region, double* __restrict__ out,
+                                   size_t rs_stride) {
     double* red = reinterpret_cast<double*>(tfft_smem);                 // [256][2]
     const int e = blockIdx.x, x = e % region, y = (e / region) % region, p = e / (region * region);
+    rowsum += (size_t)blockIdx.y * rs_stride;
+    out += (size_t)blockIdx.y * 3 * region * region;
     double re = 0, im = 0;
     for (int n = threadIdx.x; n < H; n += blockDim.x) {
         double c, s; unit_2pi((long long)y * n, PH, c, s);
@@ -2788,7 +2884,7 @@ hipError_t launch_rows_inv(const float2* in, uint8_t* rgb, const float2* tw_pw, 
     return hipSuccess;
 }
 
-template <int LOGL, int SIGN, int MODE = COLS_PLAIN, bool DC = false, bool TW = false, bool FULL = false, bool PH = false>
+template <int LOGL, int SIGN, int MODE = COLS_PLAIN, bool DC = false, bool TW = false, bool FULL = false, bool PH = false, bool PI = false>
 static hipError_t launch_cols_t(const float2* in, float2* out, const float2* tw, const ColParams& P, int n_planes,
                                 hipStream_t s) {
     constexpr int L = 1 << LOGL, E = elems_for(L), T = L / E, C = 16;
@@ -2803,7 +2899,7 @@ static hipError_t launch_cols_t(const float2* in, float2* out, const float2* tw,
         // only for the statistics, whose classification / histogram live in that store loop)
         const int rows_out_max = P.out_a * (L - 1) + P.out_b * (P.G - 1);
         if ((LOGL >= 6 || MODE == COLS_STAT || P.hist_sel) && rows_out_max < P.out_rows && P.M % C == 0 && Geff % gpb == 0)
-            return launch_cols_t<LOGL, SIGN, MODE, DC, TW, true, PH>(in, out, tw, P, n_planes, s);
+            return launch_cols_t<LOGL, SIGN, MODE, DC, TW, true, PH, PI>(in, out, tw, P, n_planes, s);
         if (MODE == COLS_STAT) return hipErrorInvalidValue;      // the in-register classification lives in the unpredicated store loop only
     }
     const size_t lds0 = (size_t)gpb * L * C * sizeof(float2) + (DC ? (size_t)gpb * L * sizeof(float2) : 0) + (TW ? (size_t)gpb * L * sizeof(float2) : 0) +
@@ -2834,13 +2930,31 @@ static hipError_t launch_cols_t(const float2* in, float2* out, const float2* tw,
         if (fixed + (size_t)P.PH * (P.M + 1) > P.st_cand_stride) return hipErrorInvalidValue;
         Q.st_cand_fixed = (unsigned)fixed;
     }
-    auto k = k_fft_cols<LOGL, SIGN, MODE, DC, TW, FULL, PH>;
+    auto k = k_fft_cols<LOGL, SIGN, MODE, DC, TW, FULL, PH, PI>;
     if (lds_total > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_total);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k, grid, block, lds_total, s, in, out, tw, Q);
     return hipGetLastError();
+}
+// one walk per image (ColParams::rd_walks): the bucket modes with PI, the same choices as below.  launch_cols checked the fields
+static hipError_t launch_cols_walks(const float2* in, float2* out, const float2* tw_ph, const ColParams& P, int logl, int sign,
+                                    int n_planes, hipStream_t s) {
+    if (!P.rd_bins) return hipErrorInvalidValue;
+    const bool phase = P.em_jp || P.em_med;
+#define L_(n, MODE, DCF, TWF, PHF) launch_cols_t<(n <= 9 ? n : 9), (MODE == COLS_EMBED ? -1 : +1), MODE, DCF, TWF, false, PHF, true>(in, out, tw_ph, P, n_planes, s)
+#define GW(n, MODE, PHF) (P.dc_ah ? L_(n, MODE, true, false, PHF) : L_(n, MODE, false, false, PHF))
+#define F(n)                                                                                                             \
+    return sign < 0 ? (phase ? (P.tw_out ? L_(n, COLS_EMBED, false, true, true) : L_(n, COLS_EMBED, false, false, true))   \
+                             : (P.tw_out ? L_(n, COLS_EMBED, false, true, false) : L_(n, COLS_EMBED, false, false, false))) \
+         : (P.em_on && P.st_sel) ? GW(n, COLS_STAT, false) : P.em_on ? GW(n, COLS_EMIT, false)                            \
+         : P.em_jp ? GW(n, COLS_READ, true) : GW(n, COLS_READ, false)
+    TFFT_DISPATCH_LOG(logl, F)
+#undef F
+#undef GW
+#undef L_
+    return hipSuccess;
 }
 hipError_t launch_cols(const float2* in, float2* out, const float2* tw_ph, const ColParams& P, int logl, int sign,
                        int n_planes, hipStream_t s) {
@@ -2857,6 +2971,7 @@ hipError_t launch_cols(const float2* in, float2* out, const float2* tw_ph, const
     if ((P.em_jp || P.em_med) && !((sign < 0 && P.em_on) || (sign > 0 && P.rd_bins && !P.em_on))) return hipErrorInvalidValue;
     if (P.em_med && sign > 0) return hipErrorInvalidValue;
     const bool phase = P.em_jp || P.em_med;
+    if (P.rd_walks) return launch_cols_walks(in, out, tw_ph, P, logl, sign, n_planes, s);
 #define G(n, MODE)                                                                      \
     (P.dc_ah ? launch_cols_t<(n <= 9 ? n : 9), +1, MODE, true>(in, out, tw_ph, P, n_planes, s) \
              : launch_cols_t<(n <= 9 ? n : 9), +1, MODE, false>(in, out, tw_ph, P, n_planes, s))
@@ -2902,6 +3017,42 @@ hipError_t launch_bucket_bins(const tfft_bin* bins, const uint32_t* bit_index, u
     hipLaunchKernelGGL(k_bucket_scan_b, dim3(1), dim3(1024), 1024 * sizeof(unsigned), s, totals, nblk, off, nb);
     hipLaunchKernelGGL(k_bucket_scan_c, dim3(nblk), dim3(1024), 0, s, off, totals, nb);
     hipLaunchKernelGGL(k_bucket_fill, dim3(blocks), dim3(256), lds, s, bins, bit_index, n, PH, PW, G, cnt, off, out, force_global);
+    return hipGetLastError();
+}
+hipError_t launch_bucket_walks(const tfft_bin* bins, uint64_t n, int n_images, int PH, int PW, int G, unsigned* cnt, unsigned* off, TileBin* out,
+                               int* err, hipStream_t s) {
+    if (n == 0 || n_images <= 0) return hipErrorInvalidValue;
+    const int M = PW >> 1, ntiles = (M + 15) >> 4;
+    const unsigned nb = 3u * (unsigned)ntiles * (unsigned)G, nbi = nb + 1;
+    const uint64_t nbt = (uint64_t)nb * (uint64_t)n_images + 1;      // + the invalid bins' bucket
+    if (nbt > 1024ull * 1024ull || (uint64_t)n * (uint64_t)n_images > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)nbt * sizeof(unsigned), s);
+    if (e != hipSuccess) return e;
+    // chunks of at least 8192 bins per workgroup: the flush of an LDS histogram costs up to nb + 1 global atomics
+    int chunks = (int)((n + 8191) / 8192);
+    if (chunks < 1) chunks = 1;
+    if ((uint64_t)chunks * (uint64_t)n_images > 65535ull) chunks = 65535 / n_images > 0 ? 65535 / n_images : 1;
+    const size_t lds = nbi <= BUCKET_LCAP ? (size_t)nbi * sizeof(unsigned) : 16;
+    hipLaunchKernelGGL(k_bucket_count_walks, dim3((unsigned)(chunks * n_images)), dim3(256), lds, s, bins, n, chunks, PH, PW, G, nb, cnt, err);
+    const int nblk = (int)((nbt + 1023) / 1024);
+    unsigned* totals = off + nbt + 1;                             // the offsets buffer holds nbt + 1 + nblk words
+    hipLaunchKernelGGL(k_bucket_scan_a, dim3(nblk), dim3(1024), 1024 * sizeof(unsigned), s, cnt, off, totals, (int)nbt);
+    hipLaunchKernelGGL(k_bucket_scan_b, dim3(1), dim3(1024), 1024 * sizeof(unsigned), s, totals, nblk, off, (int)nbt);
+    hipLaunchKernelGGL(k_bucket_scan_c, dim3(nblk), dim3(1024), 0, s, off, totals, (int)nbt);
+    hipLaunchKernelGGL(k_bucket_fill_walks, dim3((unsigned)(chunks * n_images)), dim3(256), lds, s, bins, n, chunks, PH, PW, G, nb, cnt, off, out);
+    return hipGetLastError();
+}
+hipError_t launch_gather_bits_walks(const TileBin* ent, const uint8_t* bits, const uint8_t* hdr, const uint8_t* pay, uint64_t plen, uint64_t n,
+                                    uint64_t limit, int n_images, uint8_t* out, hipStream_t s) {
+    if (n == 0 || n_images <= 0) return hipSuccess;
+    const uint64_t total = n * (uint64_t)n_images;
+    hipLaunchKernelGGL(k_gather_bits_walks, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ent, bits, hdr, pay, plen, n, limit, total, out);
+    return hipGetLastError();
+}
+hipError_t launch_gather_jitter_walks(const TileBin* ent, const float* jitter, uint64_t n, int n_images, float2* out, hipStream_t s) {
+    if (n == 0 || n_images <= 0) return hipSuccess;
+    const uint64_t total = n * (uint64_t)n_images;
+    hipLaunchKernelGGL(k_gather_jitter_walks, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ent, jitter, n, total, out);
     return hipGetLastError();
 }
 hipError_t launch_gather_bits(const TileBin* ent, const unsigned* n_ent, const uint8_t* bits, const uint8_t* hdr, const uint8_t* pay, uint64_t plen,
@@ -3132,9 +3283,16 @@ hipError_t launch_export_full(const float2* spec, int PH, int PW, int PWout, flo
 }
 hipError_t launch_lowfreq_f64(const uint8_t* rgb, int W, int H, int PW, int PH, int center, int region, double2* rowsum, double* out,
                               hipStream_t s) {
-    if (region < 1 || region > 8) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_lowfreq_rows_f64, dim3(H), dim3(32, region), (size_t)region * 32 * 6 * sizeof(double), s, rgb, W, PW, center, region, rowsum);
-    hipLaunchKernelGGL(k_lowfreq_cols_f64, dim3(3 * region * region), dim3(256), 512 * sizeof(double), s, rowsum, H, PH, center, region, out);
+    return launch_lowfreq_f64_batch(rgb, W, H, PW, PH, center, region, 1, rowsum, 0, out, s);
+}
+hipError_t launch_lowfreq_f64_batch(const uint8_t* rgb, int W, int H, int PW, int PH, int center, int region, int n_images, double2* rowsum,
+                                    size_t rowsum_stride, double* out, hipStream_t s) {
+    if (region < 1 || region > 8 || n_images < 1 || n_images > 65535) return hipErrorInvalidValue;
+    const size_t img_bytes = (size_t)W * H * 3;
+    hipLaunchKernelGGL(k_lowfreq_rows_f64, dim3(H, n_images), dim3(32, region), (size_t)region * 32 * 6 * sizeof(double), s, rgb, W, PW, center, region,
+                       rowsum, img_bytes, rowsum_stride);
+    hipLaunchKernelGGL(k_lowfreq_cols_f64, dim3(3 * region * region, n_images), dim3(256), 512 * sizeof(double), s, rowsum, H, PH, center, region, out,
+                       rowsum_stride);
     return hipGetLastError();
 }
 

@@ -18,7 +18,9 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <new>
+#include <thread>
 #include <vector>
 
 #include "../../include/turtlefft_hip.h"
@@ -271,6 +273,49 @@ int tfft_walk_jitter(const uint8_t keys_rgb[96], const tfft_bin* bins, uint64_t 
         if (bins[i].plane > 2) return TFFT_E_BIN_RANGE;
         out[i] = ks[bins[i].plane].jitter(max_jitter);                // S:719, S:1208
     }
+    return TFFT_OK;
+}
+
+// One walk per image (own keys, cover-dependent paths): image i's walk key and plane keys at keys + 128*i (walk | r | g | b, S:1054-1063),
+// its n_bins positions at bins_out + i*n_bins and their jitter at jitter_out + i*n_bins -- exactly what tfft_walk_create + tfft_walk_next +
+// tfft_walk_jitter give for that key.  The walks are independent: images are handed out to up to n_threads threads (the caller sizes the
+// pool; nothing here looks at the machine's core count).  An exhausted walk leaves its status and zeros behind the positions it found.
+int tfft_walks_build(int n, const uint8_t* keys, int ph, int pw, double rmin, double rmax, double density, double max_jitter,
+                     uint64_t n_bins, int n_threads, tfft_bin* bins_out, float* jitter_out, int32_t* status_out) {
+    if (n < 0 || (n && (!keys || !bins_out || !status_out)) || ph < 1 || pw < 1 || ph > 65536 || pw > 65536) return TFFT_E_INVALID;
+    if (n == 0) return TFFT_OK;
+    std::atomic<int> next(0);
+    auto one = [&](int i) -> int {
+        const uint8_t* k = keys + (size_t)128 * i;
+        tfft_bin* b = bins_out + (size_t)i * n_bins;
+        float* j = jitter_out ? jitter_out + (size_t)i * n_bins : nullptr;
+        tfft_walk* w = nullptr;
+        int rc = tfft_walk_create(k, ph, pw, rmin, rmax, density, &w);
+        if (rc == TFFT_OK) {
+            // positions the walk did not reach stay zero (a short walk is reported, not padded with something that looks valid)
+            memset((void*)b, 0, (size_t)n_bins * sizeof(tfft_bin));
+            rc = tfft_walk_next(w, n_bins, b, nullptr);
+            tfft_walk_destroy(w);
+        }
+        if (j) {
+            if (rc == TFFT_OK) rc = tfft_walk_jitter(k + 32, b, n_bins, max_jitter, j);
+            else memset(j, 0, (size_t)n_bins * sizeof(float));
+        }
+        return rc;
+    };
+    auto worker = [&]() {
+        for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) status_out[i] = one(i);
+    };
+    int nt = n_threads < 1 ? 1 : n_threads;
+    if (nt > n) nt = n;
+    std::vector<std::thread> pool;
+    try {
+        for (int t = 1; t < nt; t++) pool.emplace_back(worker);
+    } catch (...) {      // fewer threads than asked for: the ones there (and this one) take every image
+    }
+    worker();
+    for (auto& t : pool) t.join();
+    for (int i = 0; i < n; i++) if (status_out[i] != TFFT_OK) return status_out[i];      // (the first image's failure; every status is in status_out)
     return TFFT_OK;
 }
 
