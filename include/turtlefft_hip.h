@@ -277,6 +277,31 @@ int tfft_extract_stream_batch_walks(tfft_ctx* ctx, int n_images, const uint8_t* 
                                     const float* jitter, uint64_t n_bins, int adaptive, double alpha, uint8_t* header_out,
                                     uint8_t* payload_out, uint64_t max_payload_len, int32_t* status_out,
                                     uint8_t* raw_bits_out /* or NULL */);
+/* ------------------------------------------------------ fitted embed: stego of non-power-of-two covers that reads back
+ * The embed changes bins of the zero-padded next_pow2 spectrum and the inverse crops back to W x H: on a cover whose sides are not
+ * powers of two the crop loses much of every change and the stego does not read back (in the reference either).  This separate,
+ * non-default mode fits the stego instead, for 0 < alpha < pi/2, where the reader's decision is the side of a line (bit 1 <=>
+ * Im(F e^{-ij}) >= 0): after the walks embed, every chunk alternates a forward transform of the rounded stego, a correction of the deltas
+ * of the bins that read on the wrong side of a margin mu = max(margin * |F0| * sin(alpha_k), 3 * sqrt(W*H/24)) and the delta inverse,
+ * until every image reads every stream bit right with at least mu/2 to spare or max_iters corrections are done.
+ * The stego is an ordinary one: the unmodified extractors (tfft_extract_stream_batch_walks*, the reference CLI) read it.
+ * Semantics, state rules, errors and limits of tfft_embed_stream_batch_walks[_dev], and:
+ *   alpha must lie in (0, pi/2), max_iters >= 0 and margin > 0 (default 0.5), else TFFT_E_INVALID;
+ *   iters_out (int32 per image, or NULL): corrections applied to the image, -1 if it did not converge within max_iters (not an error:
+ *   the stego is written);  wrong_out (uint32 per image, or NULL): stream bits that read wrong from the returned bytes;
+ *   max_iters = 0 returns the bytes and usable_out of tfft_embed_stream_batch_walks[_dev] (and the counts of those bytes);
+ *   rgb_out may be rgb (each chunk's covers are copied first); the call synchronises once per iteration to read the counts.
+ * The host form stages one chunk of n_slots images at a time. */
+int tfft_embed_stream_batch_fit_dev(tfft_ctx* ctx, int n_images, const void* rgb_dev, int w, int h, int center,
+                                    const void* bins_dev, const void* jitter_dev, uint64_t n_bins, int adaptive,
+                                    const void* header_dev, const void* payload_dev, uint64_t payload_len,
+                                    double alpha, double rmin, double rmax, double magmin, int max_iters, double margin,
+                                    void* usable_out_dev, void* iters_out_dev, void* wrong_out_dev, void* rgb_out_dev);
+int tfft_embed_stream_batch_fit(tfft_ctx* ctx, int n_images, const uint8_t* rgb, int w, int h, int center, const tfft_bin* bins,
+                                const float* jitter, uint64_t n_bins, int adaptive, const uint8_t* header, const uint8_t* payload,
+                                uint64_t payload_len, double alpha, double rmin, double rmax, double magmin, int max_iters, double margin,
+                                uint64_t* usable_out /* or NULL */, int32_t* iters_out /* or NULL */, uint32_t* wrong_out /* or NULL */,
+                                uint8_t* rgb_out);
 /* compute_cover_hash's magnitudes (S:428-436) for the n_images images of a batch (device pointers, image i at rgb + i*w*h*3):
  * out = n_images*3*region*region doubles, image i's at out + i*3*region*region -- the same values, bit for bit, as tfft_lowfreq_mag on
  * each image alone (same kernels, same summation order).  Needs no forward call and leaves the slots alone; does not synchronise.

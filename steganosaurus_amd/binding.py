@@ -78,6 +78,10 @@ SYMBOLS = {
     "tfft_embed_stream_batch_walks": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _u64, _i, _vp, _vp, _u64, _d, _d, _d, _d, _vp, _vp]),
     "tfft_extract_stream_batch_walks": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _u64, _i, _d, _vp, _vp, _u64, _vp, _vp]),
     "tfft_lowfreq_mag_batch_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "tfft_embed_stream_batch_fit_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _u64, _i, _vp, _vp, _u64, _d, _d, _d, _d, _i, _d,
+                                             _vp, _vp, _vp, _vp]),
+    "tfft_embed_stream_batch_fit": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _u64, _i, _vp, _vp, _u64, _d, _d, _d, _d, _i, _d,
+                                         _vp, _vp, _vp, _vp]),
     "tfft_walks_build": (_i, [_i, _vp, _i, _i, _d, _d, _d, _d, _u64, _i, _vp, _vp, _vp]),
     "tfft_profile_stage": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _u64, _d, C.POINTER(C.c_float), _pi]),
     "tfft_timer_begin": (_i, [_vp]),
@@ -410,6 +414,28 @@ class Context:
         _check(self.lib.tfft_extract_stream_batch_walks(self.h, n, _ptr(rgb), w, h, int(center), _ptr(bins), _ptr(jit), bins.shape[1],
                                                         int(adaptive), alpha, _ptr(header_out), _ptr(payload_out), payload_out.shape[1],
                                                         _ptr(status_out), _ptr(raw_bits_out)), "tfft_extract_stream_batch_walks")
+
+    def embed_stream_batch_fit_dev(self, n_images, rgb_ptr, w, h, bins_ptr, jitter_ptr, n_bins, header_ptr, payload_ptr, payload_len,
+                                   out_ptr, adaptive=False, alpha=0.5, center=False, rmin=0.05, rmax=0.45, magmin=0.01, max_iters=16,
+                                   margin=0.5, usable_ptr=None, iters_ptr=None, wrong_ptr=None):
+        """the walks embed fitted to survive the crop of a non-power-of-two cover: iters (int32 per image, -1 = not converged) and
+        wrong (uint32 per image, stream bits that read wrong from the stego) are optional device pointers"""
+        _check(self.lib.tfft_embed_stream_batch_fit_dev(self.h, n_images, _ptr(rgb_ptr), w, h, int(center), _ptr(bins_ptr), _ptr(jitter_ptr),
+                                                        n_bins, int(adaptive), _ptr(header_ptr), _ptr(payload_ptr), payload_len, alpha, rmin,
+                                                        rmax, magmin, int(max_iters), margin, _ptr(usable_ptr), _ptr(iters_ptr), _ptr(wrong_ptr),
+                                                        _ptr(out_ptr)), "tfft_embed_stream_batch_fit_dev")
+
+    def embed_stream_batch_fit_host(self, rgb, bins, header, payload, out, jitter=None, adaptive=False, usable=None, iters=None, wrong=None,
+                                    alpha=0.5, center=False, rmin=0.05, rmax=0.45, magmin=0.01, max_iters=16, margin=0.5):
+        """rgb/out: (n,H,W,3) uint8; bins: (n, n_bins) BIN_DTYPE; jitter: (n, n_bins) float32 or None; usable (uint64), iters (int32),
+        wrong (uint32): (n,) arrays or None"""
+        n, h, w = rgb.shape[:3]
+        bins = np.ascontiguousarray(bins, BIN_DTYPE)
+        jit = None if jitter is None else np.ascontiguousarray(jitter, np.float32)
+        _check(self.lib.tfft_embed_stream_batch_fit(self.h, n, _ptr(rgb), w, h, int(center), _ptr(bins), _ptr(jit), bins.shape[1], int(adaptive),
+                                                    _ptr(header), _ptr(payload), payload.shape[1] if payload is not None else 0, alpha, rmin,
+                                                    rmax, magmin, int(max_iters), margin, _ptr(usable), _ptr(iters), _ptr(wrong), _ptr(out)),
+               "tfft_embed_stream_batch_fit")
 
     def lowfreq_mag_batch_dev(self, n_images, rgb_ptr, w, h, region, out_ptr, center=False):
         """compute_cover_hash's magnitudes of n images: out = n*3*region*region doubles (device)"""

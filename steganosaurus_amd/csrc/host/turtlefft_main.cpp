@@ -32,6 +32,7 @@ struct Params {     // S:375-381
     uint32_t pbkdf2_iter = 600000;
     bool adaptive_alpha = false;
     bool cover_dependent_path = false;
+    bool fit_crop = false;          // embed only, not in the reference: fit the stego so that it survives the crop to W x H
 };
 struct Args {       // S:839-845
     std::string mode, inPath, outPath, secret, pass, keyBase64, keyOutPath, wrapPass;
@@ -47,6 +48,7 @@ void usage() {
             "  turtlefft embed   --in host.png --out stego.png --secret TEXT (--pass PW | --key KEY_BASE64)\n"
             "      [--alpha 0.5 --jitter 0 --density 0.7 --rmin 0.05 --rmax 0.45 --magmin 0.01 --center 0]\n"
             "      [--pbkdf2_iter 600000 --adaptive_alpha 0 --cover_dependent_path 0 --wrap-pass PW]\n"
+            "      [--fit_crop 0]  1: fit the stego so that covers whose sides are not powers of two read back\n"
             "  turtlefft extract --in stego.png (--pass PW | --key KEY_BASE64)\n"
             "      [same tuning options as embed]\n"
             "  The 2-D FFT / phase embedding runs on an AMD MI355X through libturtlefft_hip.so.\n");
@@ -80,6 +82,7 @@ const OptSpec kOptions[] = {
     {"--center", OptKind::Flag, nullptr, nullptr, &Params::center, nullptr},
     {"--adaptive_alpha", OptKind::Flag, nullptr, nullptr, &Params::adaptive_alpha, nullptr},
     {"--cover_dependent_path", OptKind::Flag, nullptr, nullptr, &Params::cover_dependent_path, nullptr},
+    {"--fit_crop", OptKind::Flag, nullptr, nullptr, &Params::fit_crop, nullptr},
     {"--pbkdf2_iter", OptKind::Count, nullptr, nullptr, nullptr, &Params::pbkdf2_iter},
 };
 
@@ -181,7 +184,7 @@ void do_embed(const Args& A) {      // S:907-1109
     if (using_raw_key && !decode_or_unwrap_key(A.keyBase64, A.wrapPass, A.P.pbkdf2_iter, master_key))
         die("Failed to decode/unwrap key from --key argument");
     open_image(A, S, rgb, using_raw_key, master_key);
-    std::vector<uint8_t>().swap(rgb);
+    if (!A.P.fit_crop) std::vector<uint8_t>().swap(rgb);      // (the fitted embed adds to the cover again and again)
 
     std::array<uint8_t, 16> salt{};
     { std::random_device rd; for (auto& b : salt) b = (uint8_t)rd(); }                  // S:927-929
@@ -205,10 +208,25 @@ void do_embed(const Args& A) {      // S:907-1109
         jit.resize(bins.size());
         tf(tfft_walk_jitter(S.sub + 32, bins.data(), bins.size(), A.P.jitter, jit.data()), "jitter");
     }
-    tf(tfft_embed_bins(S.ctx, 0, bins.data(), bits.data(), jit.empty() ? nullptr : jit.data(), bins.size(), A.P.alpha,
-                       A.P.adaptive_alpha, S.med), "embed");
     std::vector<uint8_t> out((size_t)S.W * S.H * 3);
-    tf(tfft_inverse_rgb8(S.ctx, 0, out.data()), "inverse transform");
+    if (A.P.fit_crop) {
+        // the walk and jitter above through the fitted batch embed (one image): the stream's header and payload bytes out of its
+        // repetition code, every 3rd / 7th bit
+        std::vector<uint8_t> hb(HEADER_LEN * 8), pb((bits.size() - HEADER_LEN * 24) / 7);
+        for (size_t i = 0; i < hb.size(); i++) hb[i] = bits[3 * i];
+        for (size_t i = 0; i < pb.size(); i++) pb[i] = bits[HEADER_LEN * 24 + 7 * i];
+        const std::vector<uint8_t> header = bytes_from_bits(hb), payload = bytes_from_bits(pb);
+        int32_t iters = 0;
+        uint32_t wrong = 0;
+        tf(tfft_embed_stream_batch_fit(S.ctx, 1, rgb.data(), S.W, S.H, A.P.center, bins.data(), jit.empty() ? nullptr : jit.data(), bins.size(),
+                                       A.P.adaptive_alpha, header.data(), payload.data(), payload.size(), A.P.alpha, A.P.rmin, A.P.rmax,
+                                       A.P.magmin, 16, 0.5, nullptr, &iters, &wrong, out.data()), "embed");
+        if (iters < 0) fprintf(stderr, "Warning: the fitted stego did not converge; %u of %zu stream bits read wrong.\n", wrong, bits.size());
+    } else {
+        tf(tfft_embed_bins(S.ctx, 0, bins.data(), bits.data(), jit.empty() ? nullptr : jit.data(), bins.size(), A.P.alpha,
+                           A.P.adaptive_alpha, S.med), "embed");
+        tf(tfft_inverse_rgb8(S.ctx, 0, out.data()), "inverse transform");
+    }
     if (!png_write_rgb8(A.outPath, out.data(), S.W, S.H)) die("PNG write failed: %s", A.outPath.c_str());
     fprintf(stdout, "Embedded %zu bits into %s (payload %u bytes, ver=2, salt/nonce in header)\n", bits.size(),
             A.outPath.c_str(), (unsigned)A.secret.size());

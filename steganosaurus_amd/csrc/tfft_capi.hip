@@ -142,6 +142,10 @@ struct tfft_ctx {
     int fuse = 1;
     int fuse_wide = 1;
     int fuse_live = 1;                    // TFFT_FUSE_LIVE=0: the fused forward kernel with a wave (pair) and a slab for all 8 rows of a group (A/B)
+    // the fitted embed (tfft_embed_stream_batch_fit*): per bucket entry of a chunk the corrected delta and the margin; per image the
+    // count partials, the counts, and the host form's iteration / wrong-bit outputs
+    float2* fit_d = nullptr; float* fit_mu = nullptr; uint64_t fit_cap = 0;
+    unsigned* fit_part = nullptr; unsigned* fit_cnt = nullptr; int32_t* fit_iters = nullptr; uint32_t* fit_wrong = nullptr;
 
     uint8_t* img(int i) const { return img_pool + (size_t)i * img_stride_b; }
     float2* spec(int i) const { return spec_pool + (size_t)i * slot_stride; }
@@ -227,7 +231,7 @@ void invalidate_graphs(tfft_ctx* c);      // cached launch sequences hold raw de
 static void copy_embed_fields(ColParams& cp, const ColParams& e, bool inverse) {
     cp.rd_bins = e.rd_bins; cp.rd_off = e.rd_off; cp.trash = e.trash; cp.rd_walks = e.rd_walks;
     cp.em_n = e.em_n; cp.em_cos = e.em_cos; cp.em_sin = e.em_sin; cp.em_fl = e.em_fl; cp.em_pb = e.em_pb; cp.em_on = 1; cp.em_m2 = e.em_m2;
-    if (inverse) { cp.em_jp = e.em_jp; cp.em_med = e.em_med; cp.em_alpha = e.em_alpha; }      // (the phase options belong to COLS_EMBED)
+    if (inverse) { cp.em_jp = e.em_jp; cp.em_med = e.em_med; cp.em_alpha = e.em_alpha; cp.em_dsrc = e.em_dsrc; }      // (the phase options belong to COLS_EMBED)
     cp.st_sel = e.st_sel; cp.st_cand = e.st_cand; cp.st_cand_stride = e.st_cand_stride; cp.st_partial = e.st_partial; cp.st_amb = e.st_amb;
     cp.st_col0 = e.st_col0; cp.st_slo = e.st_slo; cp.st_shi = e.st_shi; cp.st_cap = e.st_cap; cp.st_PW = e.st_PW;
 }
@@ -654,6 +658,7 @@ int tfft_destroy(tfft_ctx* c) {
     (void)hipFree(c->img_pool); (void)hipFree(c->spec_pool); (void)hipFree(c->tmp_pool); (void)hipFree(c->cand_pool);
     (void)hipFree(c->col0_pool);
     (void)hipFree(c->sel); (void)hipFree(c->med); (void)hipFree(c->partial); (void)hipFree(c->amb); (void)hipFree(c->usable); (void)hipFree(c->err); (void)hipFree(c->ex_cand); (void)hipFree(c->ex_val); (void)hipFree(c->ex_below); (void)hipFree(c->ex_n); for (auto& kv : c->ex_table) (void)hipFree(kv.second); (void)hipFree(c->trash); (void)hipFree(c->bit_index); (void)hipFree(c->last_row); (void)hipFree(c->ph_jit);
+    (void)hipFree(c->fit_d); (void)hipFree(c->fit_mu); (void)hipFree(c->fit_part); (void)hipFree(c->fit_cnt); (void)hipFree(c->fit_iters); (void)hipFree(c->fit_wrong);
     for (auto& b : c->tb) { (void)hipFree(b.cnt); (void)hipFree(b.off); (void)hipFree(b.ent); (void)hipFree(b.fl); (void)hipFree(b.pb); (void)hipFree(b.jp); }
     for (auto& kv : c->tw) (void)hipFree(kv.second);
     for (auto& kv : c->dc) (void)hipFree(kv.second);
@@ -1957,6 +1962,181 @@ int tfft_extract_stream_batch_walks(tfft_ctx* c, int n_images, const uint8_t* rg
     StreamIO io; io.header_out = header_out; io.payload_out = payload_out; io.max_plen = max_payload_len; io.status_out = status_out;
     const WalkSrc ws{jitter, adaptive ? 1 : 0};
     return batch_host(c, false, n_images, rgb, w, h, center, bins, nullptr, n_bins, alpha, 0, 0, 0, nullptr, nullptr, raw_bits_out, &io, &ws);
+}
+
+// ---------------------------------------------------------------- fitted embed: stego that survives the crop
+// The embed changes bins of the next_pow2 spectrum and the inverse crops back to W x H, which loses much of every change.  For
+// 0 < alpha < pi/2 the reader's decision is linear in the pixels (bit 1 <=> Im(F e^{-ij}) >= 0), so "every stream bit reads right" is a set
+// of half-spaces, and alternating projections find a point in it: the corrections enforce the side, with a margin, at the listed bins; the
+// inverse keeps the W x H support, rounds and clamps.  The unrounded stego is cover + crop(IFFT(D)), D non-zero at the listed bins only,
+// so the whole state is one delta per bucket entry (fit_d); only the image the reader sees is rounded.
+//   margin floor: mu >= TFFT_FIT_KAPPA * sigma, sigma = sqrt(W*H/24) the standard deviation of Im F of one coefficient under +-1/2 pixel
+//   rounding (the reference's unnormalised transform)
+#define TFFT_FIT_KAPPA 3.0
+static const unsigned kFitMaxBlocks = 64;      // count workgroups per image (partials per image)
+
+static int ensure_fit(tfft_ctx* c, uint64_t n_bins) {
+    const uint64_t need = (uint64_t)c->n_slots * n_bins;
+    if (!c->fit_part) {
+        if (dev_alloc(c, (void**)&c->fit_part, (size_t)c->n_slots * kFitMaxBlocks * 2 * sizeof(unsigned)) ||
+            dev_alloc(c, (void**)&c->fit_cnt, (size_t)c->n_slots * 2 * sizeof(unsigned)) ||
+            dev_alloc(c, (void**)&c->fit_iters, (size_t)c->n_slots * sizeof(int32_t)) ||
+            dev_alloc(c, (void**)&c->fit_wrong, (size_t)c->n_slots * sizeof(uint32_t))) return TFFT_E_NOMEM;
+    }
+    if (c->fit_d && need <= c->fit_cap) return TFFT_OK;
+    (void)hipStreamSynchronize(c->stream);
+    invalidate_graphs(c);
+    (void)hipFree(c->fit_d); (void)hipFree(c->fit_mu); c->fit_d = nullptr; c->fit_mu = nullptr; c->fit_cap = 0;
+    const uint64_t cap = need + need / 4 + 1024;
+    if (dev_alloc(c, (void**)&c->fit_d, cap * sizeof(float2)) || dev_alloc(c, (void**)&c->fit_mu, cap * sizeof(float))) return TFFT_E_NOMEM;
+    c->fit_cap = cap;
+    return TFFT_OK;
+}
+
+// the last forward column step of `rgb` writes the values of the chunk's bucketed bins to tb.fl (COLS_EMIT; nothing else is stored
+// when the |F|^2 store is available to switch off)
+static int fit_forward(tfft_ctx* c, int g, const uint8_t* rgb, hipStream_t st) {
+    auto& tb = c->tb[0];
+    ColParams em{};
+    em.rd_bins = tb.ent; em.rd_off = tb.off; em.trash = c->trash; em.em_fl = tb.fl; em.em_pb = tb.pb; em.em_n = 0; em.rd_walks = 1;
+    if (c->stats_m2) { em.em_m2 = 2; em.st_col0 = c->col0_pool; }
+    StageMode md; md.fwd_emit = &em;
+    return enqueue_forward(c, 0, g, rgb, st, md);
+}
+
+// One chunk of g <= n_slots images in slots [0, g), on the context's stream.  cover: the chunk's covers in buffers nothing writes during
+// the call; iters: host, g entries; wrong_dev: device, g entries
+static int fit_chunk(tfft_ctx* c, int g, const uint8_t* cover, const tfft_bin* bins, const float* jit, uint64_t n_bins, int adaptive,
+                     const FrameSrc& fr, uint64_t n_bits, double alpha, double rmin, double rmax, double magmin, unsigned long long* usable,
+                     int max_iters, double margin, uint8_t* rgb_out, int32_t* iters, uint32_t* wrong_dev) {
+    hipStream_t st = c->stream;
+    const Slot& s = c->slots[0];
+    const WalkSrc ws{jit, adaptive ? 1 : 0};
+    // iteration 0: the walks embed itself (bucket build, bit and jitter gathers, forward with statistics and capacities, COLS_EMIT of F0)
+    int rc = embed_chunk(c, 0, g, cover, bins, nullptr, n_bins, alpha, rmin, rmax, magmin, usable, rgb_out, st, n_bits, &fr, &ws);
+    if (rc) return rc;
+    rc = check_err_flag(c);         // (a bin out of range: the buckets do not describe the lists)
+    if (rc) return rc;
+    auto& tb = c->tb[0];
+    if (!c->embed_delta) {          // TFFT_EMBED_DELTA=0 wrote F' into the spectrum: no buckets, no F0 in bucket order yet
+        const ColPlan pl = plan_cols(c, s.PH, s.PWi, g);
+        const int G = pl.direct ? 1 : (1 << pl.log_n1), ntiles = (s.PWi / 2 + 15) / 16;
+        rc = ensure_buckets(c, 0, n_bins, 3 * ntiles * G, true);
+        if (!rc) rc = build_buckets_walks(c, 0, bins, n_bins, g, s, G, jit, st);
+        if (rc) return rc;
+        HIPCHK(c, launch_gather_bits_walks(tb.ent, nullptr, fr.hdr, fr.pay, fr.plen, n_bins, n_bits, g, tb.pb, st));
+        rc = fit_forward(c, g, cover, st);
+        if (rc) return rc;
+    }
+    const float2* jp = jit ? tb.jp : nullptr;
+    const double sigma = sqrt((double)s.W * (double)s.H / 24.0);
+    HIPCHK(c, launch_fit_init(tb.ent, tb.fl, tb.pb, jp, bins, adaptive ? c->med : nullptr, n_bins, g, alpha, margin, TFFT_FIT_KAPPA * sigma,
+                              c->fit_d, c->fit_mu, st));
+    // a correction of a bin reaches the cropped image with W*H/(PW*PH) of its energy
+    const double gain = ((double)s.PW * (double)s.PH) / ((double)s.W * (double)s.H);
+    const unsigned nblk = (unsigned)std::min<uint64_t>(kFitMaxBlocks, (n_bins + 1023) / 1024);
+    ColParams ed{};
+    ed.rd_bins = tb.ent; ed.rd_off = tb.off; ed.trash = c->trash; ed.em_fl = c->fit_d; ed.em_pb = tb.pb; ed.em_n = 0; ed.rd_walks = 1; ed.em_dsrc = 1;
+    std::vector<unsigned> cnt((size_t)2 * g);
+    for (int i = 0; i < g; i++) iters[i] = -1;
+    for (int t = 0;; t++) {
+        rc = fit_forward(c, g, rgb_out, st);          // F_t of the bytes the reader will see
+        if (rc) return rc;
+        HIPCHK(c, launch_fit_count(tb.ent, tb.fl, tb.pb, jp, c->fit_mu, n_bins, g, nblk, c->fit_part, c->fit_cnt, wrong_dev, st));
+        HIPCHK(c, hipMemcpyAsync(cnt.data(), c->fit_cnt, cnt.size() * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        bool all = true;
+        for (int i = 0; i < g; i++) {
+            if (iters[i] < 0 && cnt[2 * i] == 0 && cnt[2 * i + 1] == 0) iters[i] = t;
+            all = all && iters[i] >= 0;
+        }
+        if (all || t >= max_iters) break;
+        // converged images keep their deltas: the inverse gives their bytes again
+        HIPCHK(c, launch_fit_correct(tb.ent, tb.fl, tb.pb, jp, c->fit_mu, c->fit_cnt, n_bins, g, gain, c->fit_d, st));
+        StageMode mi; mi.inv_embed = &ed; mi.inv_cover = cover;
+        rc = enqueue_inverse(c, 0, g, rgb_out, st, mi);
+        if (rc) return rc;
+    }
+    return TFFT_OK;
+}
+
+static int fit_args_ok(const tfft_ctx* c, int n_images, uint64_t n_bins, uint64_t payload_len, double alpha, int adaptive, int max_iters,
+                       double margin) {
+    int rc = walks_args_ok(c, n_images, n_bins, alpha, adaptive, false);
+    if (rc) return rc;
+    if (!(alpha > 0.0 && alpha < M_PI / 2) || max_iters < 0 || !(margin > 0.0)) return TFFT_E_INVALID;      // the line-side reading needs 0 < alpha < pi/2
+    if (n_bins < 912 || payload_len > (n_bins - 912) / 56) return TFFT_E_INVALID;
+    return TFFT_OK;
+}
+
+int tfft_embed_stream_batch_fit_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, const void* bins_dev,
+                                    const void* jitter_dev, uint64_t n_bins, int adaptive, const void* header_dev, const void* payload_dev,
+                                    uint64_t payload_len, double alpha, double rmin, double rmax, double magmin, int max_iters, double margin,
+                                    void* usable_out_dev, void* iters_out_dev, void* wrong_out_dev, void* rgb_out_dev) {
+    if (!c || !rgb_dev || !rgb_out_dev || !bins_dev || !header_dev || (payload_len && !payload_dev)) return TFFT_E_INVALID;
+    int rc = fit_args_ok(c, n_images, n_bins, payload_len, alpha, adaptive, max_iters, margin);
+    if (rc) return rc;
+    rc = ensure_fit(c, n_bins);
+    if (rc) return rc;
+    const uint64_t n_bits = 38ull * 24 + payload_len * 56;           // S:986-995
+    const size_t img_bytes = (size_t)w * h * 3;
+    std::vector<int32_t> iters((size_t)c->n_slots);
+    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
+        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+        rc = batch_geometry(c, g, w, h, center);
+        if (rc) return rc;
+        // every iteration adds to the ORIGINAL covers: the chunk's own copy in the slots' image buffers (rgb_out may be rgb)
+        HIPCHK(c, hipMemcpyAsync(c->img(0), (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyDeviceToDevice, c->stream));
+        const FrameSrc fr{(const uint8_t*)header_dev + (size_t)i0 * 38, (const uint8_t*)payload_dev + (size_t)i0 * payload_len, payload_len};
+        rc = fit_chunk(c, g, c->img(0), (const tfft_bin*)bins_dev + (size_t)i0 * n_bins, jitter_dev ? (const float*)jitter_dev + (size_t)i0 * n_bins : nullptr,
+                       n_bins, adaptive, fr, n_bits, alpha, rmin, rmax, magmin, usable_out_dev ? (unsigned long long*)usable_out_dev + i0 : nullptr,
+                       max_iters, margin, (uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes, iters.data(), wrong_out_dev ? (uint32_t*)wrong_out_dev + i0 : nullptr);
+        if (rc) return rc;
+        if (iters_out_dev) {
+            HIPCHK(c, hipMemcpyAsync((int32_t*)iters_out_dev + i0, iters.data(), (size_t)g * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));      // (the host array is reused by the next chunk)
+        }
+    }
+    return n_images ? check_err_flag(c) : TFFT_OK;
+}
+
+// host buffers: a chunk of n_slots images at a time through the staging buffers (covers in out_pool, the stego written over them)
+int tfft_embed_stream_batch_fit(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int h, int center, const tfft_bin* bins, const float* jitter,
+                                uint64_t n_bins, int adaptive, const uint8_t* header, const uint8_t* payload, uint64_t payload_len, double alpha,
+                                double rmin, double rmax, double magmin, int max_iters, double margin, uint64_t* usable_out, int32_t* iters_out,
+                                uint32_t* wrong_out, uint8_t* rgb_out) {
+    if (!c || !rgb || !rgb_out || !bins || !header || (payload_len && !payload)) return TFFT_E_INVALID;
+    int rc = fit_args_ok(c, n_images, n_bins, payload_len, alpha, adaptive, max_iters, margin);
+    if (rc || n_images == 0) return rc;
+    rc = pipe_init(c);
+    if (!rc) rc = ensure_stage(c, (uint64_t)c->n_slots * n_bins);
+    if (!rc) rc = ensure_stream_io(c, payload_len);
+    if (!rc) rc = ensure_fit(c, n_bins);
+    if (rc) return rc;
+    const uint64_t n_bits = 38ull * 24 + payload_len * 56;
+    const size_t img_bytes = (size_t)w * h * 3;
+    std::vector<int32_t> iters((size_t)c->n_slots);
+    hipStream_t st = c->stream;
+    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
+        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+        rc = batch_geometry(c, g, w, h, center);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->img(0), rgb + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->stage_bins, bins + (size_t)i0 * n_bins, (size_t)g * n_bins * sizeof(tfft_bin), hipMemcpyHostToDevice, st));
+        if (jitter) HIPCHK(c, hipMemcpyAsync(c->stage_jit, jitter + (size_t)i0 * n_bins, (size_t)g * n_bins * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->sio_hdr, header + (size_t)i0 * 38, (size_t)g * 38, hipMemcpyHostToDevice, st));
+        if (payload_len) HIPCHK(c, hipMemcpyAsync(c->sio_pay, payload + (size_t)i0 * payload_len, (size_t)g * payload_len, hipMemcpyHostToDevice, st));
+        const FrameSrc fr{c->sio_hdr, c->sio_pay, payload_len};
+        rc = fit_chunk(c, g, c->img(0), (const tfft_bin*)c->stage_bins, jitter ? (const float*)c->stage_jit : nullptr, n_bins, adaptive, fr, n_bits,
+                       alpha, rmin, rmax, magmin, usable_out ? c->usable : nullptr, max_iters, margin, c->out_pool, iters.data(), c->fit_wrong);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(rgb_out + (size_t)i0 * img_bytes, c->out_pool, (size_t)g * img_bytes, hipMemcpyDeviceToHost, st));
+        if (usable_out) HIPCHK(c, hipMemcpyAsync(usable_out + i0, c->usable, (size_t)g * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        if (wrong_out) HIPCHK(c, hipMemcpyAsync(wrong_out + i0, c->fit_wrong, (size_t)g * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (iters_out) memcpy(iters_out + i0, iters.data(), (size_t)g * sizeof(int32_t));
+    }
+    return check_err_flag(c);
 }
 
 int tfft_lowfreq_mag_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, int region, void* out_dev) {

@@ -83,6 +83,7 @@ struct ColParams {
     size_t plane_stride;  // float2 elements between planes (PH*M)
     size_t img_stride;    // float2 elements between images (grid.z = 3*n_images)
     int rd_walks;         // the bucket modes with one walk per image (launch_bucket_walks layout, k_fft_cols<..., PI = true>); 0 = one shared list
+    int em_dsrc;          // first inverse step of a walks embed: em_fl holds F' - F itself, in stored coordinates (COLS_EMBED_D, the fitted embed)
 };
 
 struct EmbedParams {
@@ -192,6 +193,18 @@ hipError_t launch_bucket_walks(const tfft_bin* bins, uint64_t n, int n_images, i
 hipError_t launch_gather_bits_walks(const TileBin* ent, const uint8_t* bits, const uint8_t* hdr, const uint8_t* pay, uint64_t plen, uint64_t n,
                                     uint64_t limit, int n_images, uint8_t* out, hipStream_t s);
 hipError_t launch_gather_jitter_walks(const TileBin* ent, const float* jitter, uint64_t n, int n_images, float2* out, hipStream_t s);
+// the fitted embed, over the n_images*n entries of a chunk's walks (fl: the values a COLS_EMIT step wrote, pb: the
+// bits, jp: jitter phasors or nullptr, med: 3 medians per image for adaptive alpha or nullptr):
+//   init   : d = F' - F0 (stored coordinates), mu = max(tau |F0| sin(alpha_k), mu_floor)
+//   count  : per image, entries that read wrong and entries below mu/2 -> counts[2*img], counts[2*img + 1] (and wrong_out[img] if given);
+//            nblk workgroups per image, partial = n_images*nblk*2 words
+//   correct: images whose counts are not both 0: d += gain * i e^{ij} (s*mu - u) where s*u < mu
+hipError_t launch_fit_init(const TileBin* ent, const float2* fl, const uint8_t* pb, const float2* jp, const tfft_bin* bins, const float* med,
+                           uint64_t n, int n_images, double alpha, double tau, double mu_floor, float2* d, float* mu, hipStream_t s);
+hipError_t launch_fit_count(const TileBin* ent, const float2* fl, const uint8_t* pb, const float2* jp, const float* mu, uint64_t n, int n_images,
+                            unsigned nblk, unsigned* partial, unsigned* counts, uint32_t* wrong_out, hipStream_t s);
+hipError_t launch_fit_correct(const TileBin* ent, const float2* fl, const uint8_t* pb, const float2* jp, const float* mu, const unsigned* counts,
+                              uint64_t n, int n_images, double gain, float2* d, hipStream_t s);
 // highest stored row any bin of the list touches -> *last_row (device int, reset here)
 hipError_t launch_stat_guess(const float2* mini, int PH, int PW, int Ms, size_t mini_img_stride, int n_images, SelectState* st, const struct CapParams* cap,
                              unsigned* partial, int col0_packed, hipStream_t s);

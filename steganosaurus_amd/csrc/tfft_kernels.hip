@@ -891,7 +891,11 @@ __device__ __forceinline__ int read_bit_value(float2 v, const EmbedParams& P, in
 //                  built this on the parked tile, measured it slower and shelved it; on round 3's kernels (two workgroups per CU,
 //                  no 64-byte |F|^2 stores to wait for) the step itself gets FASTER by it and the |F|^2 plane, its write and the
 //                  bracket pass over it disappear
-enum { COLS_PLAIN = 0, COLS_ROWLIMIT = 1, COLS_READ = 2, COLS_EMBED = 3, COLS_EMIT = 4, COLS_STAT = 5 };
+//   COLS_EMBED_D   COLS_EMBED with F' - F not computed from (F, bit, alpha) but taken as it is from P.em_fl: one value per bucket entry,
+//                  in the coordinates of the stored bin -- the corrected deltas of the fitted embed (tfft_embed_stream_batch_fit_dev,
+//                  DESIGN.md section 10).  One walk per image only (PI)
+enum { COLS_PLAIN = 0, COLS_ROWLIMIT = 1, COLS_READ = 2, COLS_EMBED = 3, COLS_EMIT = 4, COLS_STAT = 5, COLS_EMBED_D = 6 };
+constexpr bool embed_mode(int mode) { return mode == COLS_EMBED || mode == COLS_EMBED_D; }      // the first inverse step of a delta embed
 __device__ __forceinline__ unsigned wave_rank_of(unsigned long long m) {       // rank of this lane among the set bits of a wave mask
     return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
@@ -983,7 +987,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
             if (!(active && row < P.in_rows)) v[m] = make_float2(0.f, 0.f);
         }
     };
-    constexpr bool PF = (LOGL <= TFFT_COLS_PF_MAXLOG || (MODE == COLS_EMIT && TFFT_COLS_PFEMIT)) && MODE != COLS_EMBED;      // one tile ahead in registers (EMBED loads no tile: its lists always travel one tile ahead)
+    constexpr bool PF = (LOGL <= TFFT_COLS_PF_MAXLOG || (MODE == COLS_EMIT && TFFT_COLS_PFEMIT)) && !embed_mode(MODE);      // one tile ahead in registers (EMBED loads no tile: its lists always travel one tile ahead)
     float2 u[E], un[E];
     // c*A_W of the tile's column travels with the tile's loads (fetched where it is used it sat behind the prefetch of
     // the next tile in the in-order vmcnt queue and cost the overlap: 0.60 -> 0.87 ms)
@@ -1045,7 +1049,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
 #endif
 #define TFFT_EMBED_NE9 4
 #endif
-    constexpr int NE = (LOGL >= 9) ? (MODE == COLS_EMBED ? (LOGL == 9 ? TFFT_EMBED_NE9 : 2) : 4) : 2;
+    constexpr int NE = (LOGL >= 9) ? (embed_mode(MODE) ? (LOGL == 9 ? TFFT_EMBED_NE9 : 2) : 4) : 2;
     struct EmEntry { TileBin tb; float2 f; unsigned bit, live; };   // bucket entry, the stored value of its bin (conjugate of the bin when
                                                                     // tb.conj) and its stream bit (2: beyond the end of the stream)
     EmEntry enC[NE], enN[NE];
@@ -1053,7 +1057,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
     // the bucket offsets of the workgroup's tiles (at most NOFF: the launcher sees to it) sit in LDS: read with lgkmcnt, not vmcnt,
     // and without the branch trees a register array indexed by the tile turned into
     unsigned* lds_eo = reinterpret_cast<unsigned*>(lds_tw + (TWL ? L : 0) + blockDim.z * C) + gl * (NOFF + 2);
-    if (MODE == COLS_READ || MODE == COLS_EMBED || MODE == COLS_EMIT || MODE == COLS_STAT) {
+    if (MODE == COLS_READ || embed_mode(MODE) || MODE == COLS_EMIT || MODE == COLS_STAT) {
         const unsigned b0 = (unsigned)(((PI ? (int)blockIdx.z : plane) * P.G + (g < P.G ? g : 0)) * ntiles);      // (PI: blockIdx.z = 3*img + plane)
         for (int i = em_tid; i <= NOFF; i += em_nthr) lds_eo[i] = P.rd_off[b0 + (unsigned)imin(tile0 + i, ntiles)];
     }
@@ -1090,6 +1094,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
     // adaptive alpha (S:704-710): this image's median of the plane (workgroup uniform)
     const float em_medp = (MODE == COLS_EMBED && PH && P.em_med) ? fmaxf(1e-12f, P.em_med[3 * img + plane]) : 1.f;
     auto em_delta = [&](float2 f, unsigned bit, unsigned conj, unsigned e) -> float2 {      // write_bit_on_bin S:712-732 minus the old value
+        if (MODE == COLS_EMBED_D) return f;       // (em_fl holds the delta itself)
         const float mag = fmaxf(1e-12f, mag_of(f));
         float ca = P.em_cos, sa = P.em_sin;
         if (PH && P.em_med) sincosf(P.em_alpha * fminf(2.f, fmaxf(0.5f, mag / em_medp)), &sa, &ca);
@@ -1146,10 +1151,10 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
         WaveSync::sync();
         st_nstaged = 0;
     };
-    if (MODE == COLS_EMBED) em_entries(tile0, enC, true);
+    if (embed_mode(MODE)) em_entries(tile0, enC, true);
     if (PF && (MODE == COLS_EMIT || MODE == COLS_STAT || MODE == COLS_READ)) em_entries(tile0, enC, false);
     for (int tile = tile0; tile < tile1; tile++) {
-        if (!PF && MODE != COLS_EMBED) {      // no prefetch: this tile's loads and list entries now; another resident workgroup covers the wait
+        if (!PF && !embed_mode(MODE)) {      // no prefetch: this tile's loads and list entries now; another resident workgroup covers the wait
             if (!has_bins(tile)) continue;
             load_tile(tile, u); awc = load_aw(tile);
             if (MODE == COLS_EMIT || MODE == COLS_READ) em_entries(tile, enC, false);      // (COLS_STAT: after its classification, the registers are needed there)
@@ -1158,7 +1163,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
         // queue): past the last tile, or when the next tile has no bins to read, this tile is fetched again (cache resident, never used)
         if (PF) { const int nt = (tile + 1 < tile1 && has_bins(tile + 1)) ? tile + 1 : tile; load_tile(nt, un); awn = load_aw(nt); }
         if (PF && (MODE == COLS_EMIT || MODE == COLS_STAT || MODE == COLS_READ)) em_entries(tile + 1, enN, false);          // travels with the next tile's loads
-        if (MODE == COLS_EMBED) {
+        if (embed_mode(MODE)) {
             // the tile of F' - F: zeros but for the bins of the list (S:712-732 per bin); a tile without bins is stored as zeros.
             // The values of tile+1's bins and the entries of tile+2 are fetched now (see em_* above the loop).
             bool hb = true;
@@ -1865,6 +1870,96 @@ __global__ void k_gather_jitter_walks(const TileBin* __restrict__ ent, const flo
     const uint64_t j = ent[e].bit;
     const double jt = j < n ? (double)jitter[(e / n) * n + j] : 0.0;
     out[e] = make_float2((float)cos(jt), (float)sin(jt));
+}
+
+// ---- the fitted embed (tfft_embed_stream_batch_fit_dev) ------------------------------------------------------
+// Per bucket entry e of a chunk's walks (image e / n): f = the stored value of its bin after a COLS_EMIT step (the bin's own value is
+// conj(f) when ent[e].conj), its stream bit (2: beyond the stream) and the jitter phasor e^{ij} (or none).  For 0 < alpha < pi/2 the
+// reader's decision is the side of a line: bit 1 <=> u = Im(F e^{-ij}) >= 0 (S:734-746).
+__device__ __forceinline__ float fit_u(float2 f, unsigned conj, const float2* __restrict__ jp, uint64_t e) {
+    const float2 v = conj ? cconj(f) : f;
+    if (!jp) return v.y;
+    const float2 p = jp[e];
+    return v.y * p.x - v.x * p.y;
+}
+// from F0 (the cover's values): D0 = F' - F0 in stored coordinates (what COLS_EMBED puts into the tile) and the margin
+// mu = max(tau |F0| sin(alpha_k), floor) every entry is fitted to
+__global__ void k_fit_init(const TileBin* __restrict__ ent, const float2* __restrict__ fl, const uint8_t* __restrict__ pb, const float2* __restrict__ jp,
+                           const tfft_bin* __restrict__ bins, const float* __restrict__ med, uint64_t n, uint64_t total, float alpha, float cos_a,
+                           float sin_a, float tau, float mu_floor, float2* __restrict__ d, float* __restrict__ mu) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const unsigned bit = pb[e];
+    if (bit >= 2u) { d[e] = make_float2(0.f, 0.f); mu[e] = 0.f; return; }
+    const TileBin tb = ent[e];
+    const float2 f = fl[e];
+    const float mag = fmaxf(1e-12f, mag_of(f));
+    float ca = cos_a, sa = sin_a;
+    if (med) {          // adaptive alpha (S:704-710) with the image's median of the bin's plane
+        const uint64_t img = e / n;
+        const int plane = bins[img * n + tb.bit].plane;
+        sincosf(alpha * fminf(2.f, fmaxf(0.5f, mag / fmaxf(1e-12f, med[3 * img + plane]))), &sa, &ca);
+    }
+    float2 nv = make_float2(mag * ca, bit ? mag * sa : -mag * sa);
+    if (jp) nv = cmul(nv, jp[e]);
+    if (tb.conj) nv = cconj(nv);
+    d[e] = csub(nv, f);
+    mu[e] = fmaxf(tau * mag * sa, mu_floor);
+}
+// per image: entries that read wrong, and entries below half their margin (wrong ones included).  grid (nblk, n_images): workgroup b
+// counts its share of the image's n entries in LDS and writes ONE pair of partials, partial[(img*nblk + b)*2 ..] (no global atomics)
+__global__ void k_fit_count(const TileBin* __restrict__ ent, const float2* __restrict__ fl, const uint8_t* __restrict__ pb,
+                            const float2* __restrict__ jp, const float* __restrict__ mu, uint64_t n, unsigned* __restrict__ partial) {
+    unsigned* lc = reinterpret_cast<unsigned*>(tfft_smem);
+    if (threadIdx.x < 2) lc[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t img = blockIdx.y, nblk = gridDim.x;
+    const uint64_t per = (n + nblk - 1) / nblk, b0 = blockIdx.x * per, b1 = b0 + per < n ? b0 + per : n;
+    const uint64_t lo = img * n + b0, hi = img * n + b1;
+    unsigned wrong = 0, weak = 0;
+    for (uint64_t e = lo + threadIdx.x; e < hi; e += blockDim.x) {
+        const unsigned bit = pb[e];
+        if (bit >= 2u) continue;
+        const float u = fit_u(fl[e], ent[e].conj, jp, e);
+        const float su = bit ? u : -u;
+        wrong += (bit ? u < 0.f : u >= 0.f) ? 1u : 0u;      // (the reader's tie goes to 1)
+        weak += (su < 0.5f * mu[e]) ? 1u : 0u;          // (mu > 0: a wrong entry is a weak one too)
+    }
+    if (wrong) atomicAdd(&lc[0], wrong);
+    if (weak) atomicAdd(&lc[1], weak);
+    __syncthreads();
+    if (threadIdx.x < 2) partial[(img * nblk + blockIdx.x) * 2 + threadIdx.x] = lc[threadIdx.x];
+}
+// ... summed per image: counts[2*img] wrong, counts[2*img + 1] below half the margin; wrong_out[img] (optional) = the wrong count
+__global__ void k_fit_sum(const unsigned* __restrict__ partial, unsigned nblk, unsigned* __restrict__ counts, uint32_t* __restrict__ wrong_out) {
+    const unsigned img = blockIdx.x;
+    if (threadIdx.x != 0) return;
+    unsigned wrong = 0, weak = 0;
+    for (unsigned b = 0; b < nblk; b++) { wrong += partial[((size_t)img * nblk + b) * 2]; weak += partial[((size_t)img * nblk + b) * 2 + 1]; }
+    counts[2 * img] = wrong; counts[2 * img + 1] = weak;
+    if (wrong_out) wrong_out[img] = wrong;
+}
+// one correction: every entry of a not yet converged image with s*u < mu gets the smallest change of its bin that puts u at s*mu,
+// i e^{ij} (s*mu - u), times `gain` (the crop keeps W*H/(PW*PH) of a bin's energy: gain = PW*PH/(W*H)), added to its delta in stored
+// coordinates (conjugated for a mirror entry)
+__global__ void k_fit_correct(const TileBin* __restrict__ ent, const float2* __restrict__ fl, const uint8_t* __restrict__ pb,
+                              const float2* __restrict__ jp, const float* __restrict__ mu, const unsigned* __restrict__ counts, uint64_t n,
+                              uint64_t total, float gain, float2* __restrict__ d) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const uint64_t img = e / n;
+    if (counts[2 * img] == 0 && counts[2 * img + 1] == 0) return;      // converged: its stego stays as it is
+    const unsigned bit = pb[e];
+    if (bit >= 2u) return;
+    const TileBin tb = ent[e];
+    const float u = fit_u(fl[e], tb.conj, jp, e);
+    const float m = mu[e], target = bit ? m : -m;
+    if (bit ? u >= m : u <= -m) return;
+    const float s = (target - u) * gain;
+    const float2 p = jp ? jp[e] : make_float2(1.f, 0.f);
+    float2 dv = make_float2(-p.y * s, p.x * s);          // i e^{ij} s
+    if (tb.conj) dv = cconj(dv);
+    d[e] = cadd(d[e], dv);
 }
 
 // ---------------------------------------------------------------------------
@@ -2908,7 +3003,7 @@ static hipError_t launch_cols_t(const float2* in, float2* out, const float2* tw,
     if (MODE == COLS_PLAIN && SIGN > 0 && P.tile_step > 1) ntiles = (ntiles - P.tile_off + P.tile_step - 1) / P.tile_step;      // the statistics' sample: every tile_step-th tile
     int tpb = P.tiles_per_block > 0 ? P.tiles_per_block : 1;
     ColParams Q = P;
-    constexpr bool BUCKETS = (MODE == COLS_READ || MODE == COLS_EMBED || MODE == COLS_EMIT || MODE == COLS_STAT);
+    constexpr bool BUCKETS = (MODE == COLS_READ || embed_mode(MODE) || MODE == COLS_EMIT || MODE == COLS_STAT);
     if (BUCKETS) {          // the bucket offsets of a workgroup's tiles are staged in LDS: 16 tiles + sentinel per group
         if (tpb > 16) tpb = 16;
         Q.tiles_per_block = tpb;
@@ -2943,11 +3038,12 @@ static hipError_t launch_cols_walks(const float2* in, float2* out, const float2*
                                     int n_planes, hipStream_t s) {
     if (!P.rd_bins) return hipErrorInvalidValue;
     const bool phase = P.em_jp || P.em_med;
-#define L_(n, MODE, DCF, TWF, PHF) launch_cols_t<(n <= 9 ? n : 9), (MODE == COLS_EMBED ? -1 : +1), MODE, DCF, TWF, false, PHF, true>(in, out, tw_ph, P, n_planes, s)
+#define L_(n, MODE, DCF, TWF, PHF) launch_cols_t<(n <= 9 ? n : 9), (embed_mode(MODE) ? -1 : +1), MODE, DCF, TWF, false, PHF, true>(in, out, tw_ph, P, n_planes, s)
 #define GW(n, MODE, PHF) (P.dc_ah ? L_(n, MODE, true, false, PHF) : L_(n, MODE, false, false, PHF))
 #define F(n)                                                                                                             \
-    return sign < 0 ? (phase ? (P.tw_out ? L_(n, COLS_EMBED, false, true, true) : L_(n, COLS_EMBED, false, false, true))   \
-                             : (P.tw_out ? L_(n, COLS_EMBED, false, true, false) : L_(n, COLS_EMBED, false, false, false))) \
+    return sign < 0 ? (P.em_dsrc ? (P.tw_out ? L_(n, COLS_EMBED_D, false, true, false) : L_(n, COLS_EMBED_D, false, false, false))   \
+                      : phase ? (P.tw_out ? L_(n, COLS_EMBED, false, true, true) : L_(n, COLS_EMBED, false, false, true))   \
+                              : (P.tw_out ? L_(n, COLS_EMBED, false, true, false) : L_(n, COLS_EMBED, false, false, false))) \
          : (P.em_on && P.st_sel) ? GW(n, COLS_STAT, false) : P.em_on ? GW(n, COLS_EMIT, false)                            \
          : P.em_jp ? GW(n, COLS_READ, true) : GW(n, COLS_READ, false)
     TFFT_DISPATCH_LOG(logl, F)
@@ -2970,6 +3066,7 @@ hipError_t launch_cols(const float2* in, float2* out, const float2* tw_ph, const
     // the phase options exist in the first inverse step (COLS_EMBED) and the tile-resident read (COLS_READ) only
     if ((P.em_jp || P.em_med) && !((sign < 0 && P.em_on) || (sign > 0 && P.rd_bins && !P.em_on))) return hipErrorInvalidValue;
     if (P.em_med && sign > 0) return hipErrorInvalidValue;
+    if (P.em_dsrc && !(sign < 0 && P.em_on && P.rd_walks && !P.em_jp && !P.em_med)) return hipErrorInvalidValue;      // COLS_EMBED_D: walks, no phase options
     const bool phase = P.em_jp || P.em_med;
     if (P.rd_walks) return launch_cols_walks(in, out, tw_ph, P, logl, sign, n_planes, s);
 #define G(n, MODE)                                                                      \
@@ -3053,6 +3150,30 @@ hipError_t launch_gather_jitter_walks(const TileBin* ent, const float* jitter, u
     if (n == 0 || n_images <= 0) return hipSuccess;
     const uint64_t total = n * (uint64_t)n_images;
     hipLaunchKernelGGL(k_gather_jitter_walks, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ent, jitter, n, total, out);
+    return hipGetLastError();
+}
+hipError_t launch_fit_init(const TileBin* ent, const float2* fl, const uint8_t* pb, const float2* jp, const tfft_bin* bins, const float* med,
+                           uint64_t n, int n_images, double alpha, double tau, double mu_floor, float2* d, float* mu, hipStream_t s) {
+    if (n == 0 || n_images <= 0) return hipSuccess;
+    const uint64_t total = n * (uint64_t)n_images;
+    hipLaunchKernelGGL(k_fit_init, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ent, fl, pb, jp, bins, med, n, total, (float)alpha,
+                       (float)cos(alpha), (float)sin(alpha), (float)tau, (float)mu_floor, d, mu);
+    return hipGetLastError();
+}
+hipError_t launch_fit_count(const TileBin* ent, const float2* fl, const uint8_t* pb, const float2* jp, const float* mu, uint64_t n, int n_images,
+                            unsigned nblk, unsigned* partial, unsigned* counts, uint32_t* wrong_out, hipStream_t s) {
+    if (n == 0 || n_images <= 0 || nblk == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_fit_count, dim3(nblk, (unsigned)n_images), dim3(256), 2 * sizeof(unsigned), s, ent, fl, pb, jp, mu, n, partial);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_fit_sum, dim3((unsigned)n_images), dim3(64), 0, s, partial, nblk, counts, wrong_out);
+    return hipGetLastError();
+}
+hipError_t launch_fit_correct(const TileBin* ent, const float2* fl, const uint8_t* pb, const float2* jp, const float* mu, const unsigned* counts,
+                              uint64_t n, int n_images, double gain, float2* d, hipStream_t s) {
+    if (n == 0 || n_images <= 0) return hipSuccess;
+    const uint64_t total = n * (uint64_t)n_images;
+    hipLaunchKernelGGL(k_fit_correct, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ent, fl, pb, jp, mu, counts, n, total, (float)gain, d);
     return hipGetLastError();
 }
 hipError_t launch_gather_bits(const TileBin* ent, const unsigned* n_ent, const uint8_t* bits, const uint8_t* hdr, const uint8_t* pay, uint64_t plen,
