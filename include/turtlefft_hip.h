@@ -107,8 +107,9 @@ int tfft_median_path(tfft_ctx* ctx, int slot, int fast[3]);
 /* count_plane (S:998-1008): sum over planes of floor(c/2), c = bins in the
  * annulus [rmin,rmax]*min(PH,PW), off the axes, |F| >= thr[plane].  Synchronises.
  * EXACT like tfft_medians (same conditions): bins within 1e-3 of thr are settled on their fp64 magnitudes, so with
- * thr = magmin * tfft_medians() the count is the reference's integer.  The batched pipelines' usable_out stays the count on the
- * fp32 planes (observed 0-1 off, bound 2: a bin within fp32 rounding of the threshold), see DESIGN.md section 2. */
+ * thr = magmin * tfft_medians() the count is the reference's integer.  The batched pipelines' usable_out is the count on the
+ * fp32 planes (observed 0-1 off, bound 2: a bin within fp32 rounding of the threshold) unless tfft_set_batch_exact asks for this
+ * integer there too, see DESIGN.md sections 2 and 11. */
 int tfft_capacity(tfft_ctx* ctx, int slot, double rmin, double rmax, const double thr[3], uint64_t* usable);
 
 /* compute_cover_hash's magnitudes (S:428-436): |F[y][x]| for y,x < region (<= 8) of
@@ -174,7 +175,9 @@ int tfft_audit_forward_rgb8_f64(tfft_ctx* ctx, const uint8_t* rgb, int w, int h,
  *   embed  : forward -> [medians+capacity when usable_out != NULL] -> embed -> inverse
  *   extract: forward -> read
  * usable_out (device, n uint64) receives each image's capacity so the caller
- * can raise "Message too large" (S:1009-1012) without a sync per image.
+ * can raise "Message too large" (S:1009-1012) without a sync per image: the count
+ * on the fp32 planes (0-2 off the reference's integer), or with tfft_set_batch_exact
+ * the reference's integer itself.
  * The embed pipeline uses the linearity of S:1099-1103: stego = clamp(round(cover +
  * IFFT(F' - F))), F' - F being zero but at the bins of the list -- the modified spectrum
  * is never written, the cover buffer is read once more by the last kernel (in-place
@@ -374,6 +377,30 @@ int tfft_set_bit_index(tfft_ctx* ctx, const uint32_t* bit_index, uint64_t n);
  *           TFFT_E_INVALID -- tfft_read_bins[_dev] with the image's medians covers that case.
  * (ctx, NULL, 0, 0) clears both.  Synchronises with the context's streams.  The single-image calls keep their own arguments. */
 int tfft_set_phase_options(tfft_ctx* ctx, const float* jitter, uint64_t n, int adaptive_alpha);
+
+/* Exact capacities of the BATCHED embeds.  By default their usable_out is the count on the fp32 planes of the
+ * batch statistics, which can be 1-2 off the reference's integer (a bin within fp32 rounding of the threshold): near the boundary a caller
+ * could accept or refuse a payload ("Message too large", S:1009-1012) differently from the reference.  This opt-in mode makes usable_out
+ * the reference's integer, i.e. tfft_capacity(magmin * tfft_medians) of each image alone:
+ *   TFFT_BATCH_EXACT_OFF  : default; the fp32 counts, same kernels and launch sequence as without the setter;
+ *   TFFT_BATCH_EXACT_ALL  : every image of every call that fills usable_out is settled;
+ *   TFFT_BATCH_EXACT_NEAR : only images whose fp32 count lies within guard_bits of the call's stream length (n_bits of the bit-level
+ *                           calls, 912 + 56*payload_len of the stream calls): those whose decision the integer can change.  The default
+ *                           guard, 64 bits, is far above the largest |fp32 - exact| the tests saw (1, 32 x 1080p and 8 x 4K).
+ * Applies to tfft_embed_batch[_dev], tfft_embed_stream_batch[_dev], tfft_embed_stream_batch_walks[_dev], tfft_embed_stream_batch_fit[_dev]
+ * (the cover's capacity) and so to tfp_embed_png_batch through the context.  The stego bytes do not change: the embed, adaptive alpha
+ * included, keeps the fp32 batch medians.  With the mode on, a call that fills usable_out settles each chunk after its embed (a storing
+ * forward of the selected covers, then the fp64 rounds of tfft_medians / tfft_capacity for all of them at once); it synchronises and is
+ * never captured into or replayed from the graph cache (TFFT_GRAPHS).  Device buffers are allocated when the mode is first turned on.
+ * A mode outside 0..2 gives TFFT_E_INVALID. */
+#define TFFT_BATCH_EXACT_OFF  0   /* default: today's fp32 counts, bit for bit */
+#define TFFT_BATCH_EXACT_ALL  1   /* every image's usable_out is the reference's integer */
+#define TFFT_BATCH_EXACT_NEAR 2   /* only images whose fp32 count lies within guard_bits of the call's stream length */
+int tfft_set_batch_exact(tfft_ctx* ctx, int mode, uint64_t guard_bits);
+/* per image of the LAST batched embed call that filled usable_out: 1 exact, 0 fp32 count (mode off, not near, or no usable_out),
+ * -1 exact was asked for but could not be settled (returns the fp32 count: candidate overflow, flat spectrum, PW > 8192, W < 2).
+ * n_images larger than that call's gives TFFT_E_INVALID.  (tfp_embed_png_batch calls the context once per chunk: its last chunk's.) */
+int tfft_batch_exact_info(const tfft_ctx* ctx, int n_images, int32_t* state_out);
 
 /* ------------------------------------------------------------ measurement
  * Device-side timing of whatever was enqueued between the two calls on the

@@ -73,6 +73,8 @@ SYMBOLS = {
     "tfft_set_bit_index": (_i, [_vp, _vp, _u64]),
     "tfft_bins_register_dev": (_i, [_vp, _vp, _u64]),
     "tfft_set_phase_options": (_i, [_vp, _vp, _u64, _i]),
+    "tfft_set_batch_exact": (_i, [_vp, _i, _u64]),
+    "tfft_batch_exact_info": (_i, [_vp, _i, _vp]),
     "tfft_embed_stream_batch_walks_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _u64, _i, _vp, _vp, _u64, _d, _d, _d, _d, _vp, _vp]),
     "tfft_extract_stream_batch_walks_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _u64, _i, _d, _vp, _vp, _u64, _vp, _vp]),
     "tfft_embed_stream_batch_walks": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _u64, _i, _vp, _vp, _u64, _d, _d, _d, _d, _vp, _vp]),
@@ -252,6 +254,20 @@ class Context:
             return
         jit = np.ascontiguousarray(jitter, np.float32)
         _check(self.lib.tfft_set_phase_options(self.h, _ptr(jit), len(jit), int(adaptive)), "tfft_set_phase_options")
+
+    # modes of set_batch_exact (tfft_set_batch_exact)
+    BATCH_EXACT_OFF, BATCH_EXACT_ALL, BATCH_EXACT_NEAR = 0, 1, 2
+
+    def set_batch_exact(self, mode, guard=64):
+        """usable_out of the batched embeds: 0 the fp32 counts (default), 1 the reference's integer for every image, 2 only for images
+        whose fp32 count lies within `guard` bits of the call's stream length."""
+        _check(self.lib.tfft_set_batch_exact(self.h, int(mode), int(guard)), "tfft_set_batch_exact")
+
+    def batch_exact_info(self, n):
+        """per image of the last batched embed that filled usable_out: 1 exact, 0 fp32 count, -1 asked for but not settled"""
+        out = np.zeros(n, np.int32)
+        _check(self.lib.tfft_batch_exact_info(self.h, int(n), _ptr(out)), "tfft_batch_exact_info")
+        return out
 
     def bins_register_dev(self, bins_ptr, n):
         _check(self.lib.tfft_bins_register_dev(self.h, _ptr(bins_ptr), n), "tfft_bins_register_dev")

@@ -146,6 +146,12 @@ struct tfft_ctx {
     // count partials, the counts, and the host form's iteration / wrong-bit outputs
     float2* fit_d = nullptr; float* fit_mu = nullptr; uint64_t fit_cap = 0;
     unsigned* fit_part = nullptr; unsigned* fit_cnt = nullptr; int32_t* fit_iters = nullptr; uint32_t* fit_wrong = nullptr;
+    // tfft_set_batch_exact: the batched embeds' usable_out settled in fp64 like tfft_capacity.  The device buffers are
+    // allocated when the mode is first turned on, for n_slots images; bx_state holds the per-image states of the last call that filled usable_out
+    int bx_mode = 0; uint64_t bx_guard = 64; int bx_trace = 0;      // TFFT_BATCH_EXACT_TRACE=1: one line per settled chunk on stderr (tools/exact_cost.py)
+    std::vector<int32_t> bx_state; int bx_last_n = 0;
+    ExactWin* bx_win = nullptr; ExactCandB* bx_cand = nullptr; unsigned long long* bx_below = nullptr; unsigned* bx_n = nullptr;
+    unsigned* bx_idx = nullptr; ExactGroup* bx_grp = nullptr; double2* bx_part = nullptr; ExactVal* bx_val = nullptr; size_t bx_part_cap = 0, bx_val_cap = 0;
 
     uint8_t* img(int i) const { return img_pool + (size_t)i * img_stride_b; }
     float2* spec(int i) const { return spec_pool + (size_t)i * slot_stride; }
@@ -609,6 +615,7 @@ int tfft_create(int device, int max_w, int max_h, int n_slots, tfft_ctx** out) {
     if (const char* e = getenv("TFFT_STATS_COMPACT")) c->stats_compact = atoi(e);
     if (const char* e = getenv("TFFT_GRAPHS")) c->graph_max_images = atoi(e);
     if (const char* e = getenv("TFFT_EXACT_STATS")) c->exact_stats = atoi(e);
+    if (const char* e = getenv("TFFT_BATCH_EXACT_TRACE")) c->bx_trace = atoi(e);
     if (const char* e = getenv("TFFT_STATS_TILE")) c->stats_tile = atoi(e);
     if (const char* e = getenv("TFFT_STATS_PRIO")) c->stats_prio = atoi(e);
     if (const char* e = getenv("TFFT_STATS_FAIL_ONCE")) c->stats_fail_once = atoi(e);
@@ -659,6 +666,8 @@ int tfft_destroy(tfft_ctx* c) {
     (void)hipFree(c->col0_pool);
     (void)hipFree(c->sel); (void)hipFree(c->med); (void)hipFree(c->partial); (void)hipFree(c->amb); (void)hipFree(c->usable); (void)hipFree(c->err); (void)hipFree(c->ex_cand); (void)hipFree(c->ex_val); (void)hipFree(c->ex_below); (void)hipFree(c->ex_n); for (auto& kv : c->ex_table) (void)hipFree(kv.second); (void)hipFree(c->trash); (void)hipFree(c->bit_index); (void)hipFree(c->last_row); (void)hipFree(c->ph_jit);
     (void)hipFree(c->fit_d); (void)hipFree(c->fit_mu); (void)hipFree(c->fit_part); (void)hipFree(c->fit_cnt); (void)hipFree(c->fit_iters); (void)hipFree(c->fit_wrong);
+    (void)hipFree(c->bx_win); (void)hipFree(c->bx_cand); (void)hipFree(c->bx_below); (void)hipFree(c->bx_n); (void)hipFree(c->bx_idx); (void)hipFree(c->bx_grp);
+    (void)hipFree(c->bx_part); (void)hipFree(c->bx_val);
     for (auto& b : c->tb) { (void)hipFree(b.cnt); (void)hipFree(b.off); (void)hipFree(b.ent); (void)hipFree(b.fl); (void)hipFree(b.pb); (void)hipFree(b.jp); }
     for (auto& kv : c->tw) (void)hipFree(kv.second);
     for (auto& kv : c->dc) (void)hipFree(kv.second);
@@ -839,6 +848,257 @@ bool exact_medians(tfft_ctx* c, int slot, const float m32[3], double med[3], int
     }
     return false;
 }
+
+// ---- exact capacities of the batched embeds (tfft_set_batch_exact).  A chunk's selected covers get a storing fp32
+// forward into the slot spectra; then the single-image method (exact_medians, tfft_capacity) runs for all of them at once: one collect
+// launch (per-image windows), one evaluate launch (k_exact_eval_batch: TFFT_EXACT_K candidates of an image plane per pass over its pixels),
+// one in-order sum, one read per round.  Rounds and windows follow the single-image calls; an image settles, widens or gives up on its own.
+int bx_buffers(tfft_ctx* c) {
+    if (c->bx_win) return TFFT_OK;
+    const size_t n = (size_t)c->n_slots, nc = 3 * n * EX_CAP;
+    if (dev_alloc(c, (void**)&c->bx_win, n * sizeof(ExactWin)) || dev_alloc(c, (void**)&c->bx_cand, nc * sizeof(ExactCandB)) ||
+        dev_alloc(c, (void**)&c->bx_below, 3 * n * sizeof(unsigned long long)) || dev_alloc(c, (void**)&c->bx_n, 3 * n * sizeof(unsigned)) ||
+        dev_alloc(c, (void**)&c->bx_idx, nc * sizeof(unsigned)) || dev_alloc(c, (void**)&c->bx_grp, nc * sizeof(ExactGroup)))
+        return TFFT_E_NOMEM;
+    return TFFT_OK;
+}
+// the partials and settled values of n dense candidates (grown on demand: a round rarely holds more than a few thousand)
+int bx_value_buffers(tfft_ctx* c, size_t n, int split) {
+    const size_t np = n * (size_t)split;
+    if (np > c->bx_part_cap) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(c->bx_part); c->bx_part = nullptr; c->bx_part_cap = 0;
+        const size_t cap = np + np / 2 + 4096;
+        if (dev_alloc(c, (void**)&c->bx_part, cap * sizeof(double2))) return TFFT_E_NOMEM;
+        c->bx_part_cap = cap;
+    }
+    if (n > c->bx_val_cap) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(c->bx_val); c->bx_val = nullptr; c->bx_val_cap = 0;
+        const size_t cap = n + n / 2 + 1024;
+        if (dev_alloc(c, (void**)&c->bx_val, cap * sizeof(ExactVal))) return TFFT_E_NOMEM;
+        c->bx_val_cap = cap;
+    }
+    return TFFT_OK;
+}
+int exact_table(tfft_ctx* c, int PW, const double2** out) {
+    auto it = c->ex_table.find(PW);
+    if (it != c->ex_table.end()) { *out = it->second; return TFFT_OK; }
+    double2* t = nullptr;
+    if (dev_alloc(c, (void**)&t, (size_t)PW * sizeof(double2))) return TFFT_E_NOMEM;
+    HIPCHK(c, launch_exact_table(t, PW, c->stream));
+    c->ex_table[PW] = t;
+    *out = t;
+    return TFFT_OK;
+}
+// per (entry, plane) of a round: the candidates' settled values, the weight outside the window, whether the list fit
+struct BxList { std::vector<ExactVal> v; unsigned long long outside = 0; bool ok = false; };
+// one collect + evaluate round over the launch entries `win` (spectra at c->spec(s0) + img, covers at cov + img * img_bytes) -> out[3z + p]
+int bx_round(tfft_ctx* c, int s0, const uint8_t* cov, size_t img_bytes, const ExactCollect& P, const std::vector<ExactWin>& win,
+             std::vector<BxList>& out, unsigned* max_cand, hipStream_t st) {
+    const Slot& s = c->slots[s0];
+    const int nz = (int)win.size(), nl = 3 * nz;
+    std::vector<unsigned> n((size_t)nl);
+    std::vector<unsigned long long> below((size_t)nl);
+    HIPCHK(c, hipMemcpyAsync(c->bx_win, win.data(), (size_t)nz * sizeof(ExactWin), hipMemcpyHostToDevice, st));
+    HIPCHK(c, launch_exact_collect_batch(c->spec(s0), c->slot_stride, P, c->bx_win, nz, c->bx_cand, c->bx_below, c->bx_n, st));
+    HIPCHK(c, hipMemcpyAsync(n.data(), c->bx_n, (size_t)nl * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(below.data(), c->bx_below, (size_t)nl * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    // dense candidates of the entries whose three lists fit, in list order; workgroups of up to TFFT_EXACT_K of one list
+    std::vector<unsigned> idx;
+    std::vector<ExactGroup> grp;
+    out.assign((size_t)nl, BxList());
+    for (int z = 0; z < nz; z++) {
+        const bool fit = n[3 * z] <= (unsigned)EX_CAP && n[3 * z + 1] <= (unsigned)EX_CAP && n[3 * z + 2] <= (unsigned)EX_CAP;
+        for (int p = 0; p < 3; p++) {
+            const int l = 3 * z + p;
+            out[l].ok = fit; out[l].outside = below[l];
+            if (max_cand && n[l] > *max_cand) *max_cand = n[l];
+            if (!fit) continue;
+            for (unsigned k0 = 0; k0 < n[l]; k0 += TFFT_EXACT_K) {
+                const unsigned cnt = n[l] - k0 < (unsigned)TFFT_EXACT_K ? n[l] - k0 : (unsigned)TFFT_EXACT_K;
+                grp.push_back(ExactGroup{(unsigned)idx.size(), cnt});
+                for (unsigned k = 0; k < cnt; k++) idx.push_back((unsigned)l * EX_CAP + k0 + k);
+            }
+        }
+    }
+    if (idx.empty()) return TFFT_OK;
+    const double2* table = nullptr;
+    int rc = exact_table(c, s.PWi, &table);
+    if (rc) return rc;
+    int split = s.H / 32;                // as exact_round: the same row bands, hence the same partials
+    if (split < 1) split = 1;
+    if (split > EX_SPLIT) split = EX_SPLIT;
+    rc = bx_value_buffers(c, idx.size(), split);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->bx_idx, idx.data(), idx.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->bx_grp, grp.data(), grp.size() * sizeof(ExactGroup), hipMemcpyHostToDevice, st));
+    HIPCHK(c, launch_exact_eval_batch(cov, img_bytes, s.W, s.H, s.PWi, s.PH, s.center, c->bx_cand, c->bx_idx, c->bx_grp, (unsigned)grp.size(), split,
+                                      table, c->bx_part, st));
+    HIPCHK(c, launch_exact_sum_batch(c->bx_part, split, c->bx_cand, c->bx_idx, (unsigned)idx.size(), c->bx_val, st));
+    std::vector<ExactVal> v(idx.size());
+    HIPCHK(c, hipMemcpyAsync(v.data(), c->bx_val, v.size() * sizeof(ExactVal), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    for (size_t i = 0; i < idx.size(); i++) out[idx[i] / EX_CAP].v.push_back(v[i]);
+    return TFFT_OK;
+}
+
+// The chunk in slots [s0, s0+g): covers at cov (g images w*h*3 bytes apart, intact), fp32 medians in c->med, fp32 counts in `usable` (device).
+// Settles the images the mode selects (NEAR: |count - L| <= guard) and overwrites their counts; state[i] = 1 / 0 / -1 (tfft_batch_exact_info).
+// Synchronises st.
+int bx_settle(tfft_ctx* c, int s0, int g, const uint8_t* cov, double rmin, double rmax, double magmin, uint64_t L, unsigned long long* usable,
+              int32_t* state, hipStream_t st) {
+    for (int i = 0; i < g; i++) state[i] = 0;
+    if (!c->bx_mode || !usable || g <= 0) return TFFT_OK;
+    int rc = bx_buffers(c);
+    if (rc) return rc;
+    const Slot& s = c->slots[s0];
+    const size_t img_bytes = (size_t)s.W * s.H * 3;
+    std::vector<unsigned long long> u((size_t)g);
+    std::vector<float> m32((size_t)3 * g);
+    HIPCHK(c, hipMemcpyAsync(u.data(), usable, (size_t)g * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(m32.data(), c->med + 3 * s0, (size_t)3 * g * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    std::vector<int> sel;
+    for (int i = 0; i < g; i++) {
+        const uint64_t d = u[i] >= L ? u[i] - L : L - u[i];
+        if (c->bx_mode == TFFT_BATCH_EXACT_ALL || d <= c->bx_guard) sel.push_back(i);
+    }
+    if (sel.empty()) return TFFT_OK;
+    for (int i : sel) state[i] = -1;
+    Slot sx = s; sx.rgb_src = cov;                      // (exact_possible asks for an image to read)
+    if (!exact_possible(c, sx)) return TFFT_OK;         // W < 2, PW > 8192, TFFT_EXACT_STATS=0: the fp32 counts stay
+    const int n = (int)sel.size();
+    // the selected covers packed to the front (NEAR): in the slots' image pool; a cover already there moves down only (j <= sel[j])
+    const uint8_t* src = cov;
+    if (n < g) {
+        uint8_t* dst = c->img(s0);
+        for (int j = 0; j < n; j++)
+            if (cov + (size_t)sel[j] * img_bytes != dst + (size_t)j * img_bytes)
+                HIPCHK(c, hipMemcpyAsync(dst + (size_t)j * img_bytes, cov + (size_t)sel[j] * img_bytes, img_bytes, hipMemcpyDeviceToDevice, st));
+        src = dst;
+    }
+    rc = enqueue_forward(c, s0, n, src, st);            // the fp32 spectra the windows are taken on (one storing forward launch sequence)
+    for (int j = 0; j < n; j++) { c->slots[s0 + j].has_spec = false; c->slots[s0 + j].rgb_src = nullptr; }
+    if (rc) return rc;
+    ExactCollect P{};
+    P.PH = s.PH; P.PW = s.PWi; P.PW_full = s.PW; P.cap_cand = EX_CAP;
+    unsigned max_cand = 0;
+    int med_rounds = 0, cap_rounds = 0;
+    // medians: rank PH*PW/2, window 2e-6 widened x4, at most 5 rounds (exact_medians)
+    const unsigned long long rank = ((unsigned long long)s.PH * s.PW) / 2;
+    std::vector<double> med((size_t)3 * n);
+    std::vector<int> todo, done;
+    for (int j = 0; j < n; j++) todo.push_back(j);
+    double rel = 2e-6;
+    for (int attempt = 0; attempt < 5 && !todo.empty(); attempt++, rel *= 4.0) {
+        std::vector<ExactWin> win(todo.size());
+        for (size_t z = 0; z < todo.size(); z++) {
+            win[z].img = todo[z];
+            for (int p = 0; p < 3; p++) exact_window((double)m32[3 * sel[todo[z]] + p], rel, win[z].lo2[p], win[z].hi2[p]);
+        }
+        P.cap = 0;
+        std::vector<BxList> o;
+        rc = bx_round(c, s0, src, img_bytes, P, win, o, &max_cand, st);
+        if (rc) return rc;
+        med_rounds++;
+        std::vector<int> again;
+        for (size_t z = 0; z < todo.size(); z++) {
+            const int j = todo[z];
+            if (!o[3 * z].ok) continue;                 // a flat spectrum: gives up (state -1), as the single-image call keeps its fp32 answer
+            bool good = true;
+            for (int p = 0; p < 3 && good; p++) {
+                const BxList& b = o[3 * z + p];
+                const float mp = m32[3 * sel[j] + p];
+                unsigned long long wsum = 0; double emax = 0.0;
+                std::vector<double> mag(b.v.size());
+                for (size_t i = 0; i < b.v.size(); i++) {
+                    mag[i] = hypot(b.v[i].re, b.v[i].im);
+                    wsum += b.v[i].w; emax = fmax(emax, fabs(mag[i] - sqrt((double)b.v[i].m2)));
+                }
+                if (!(b.outside <= rank && rank < b.outside + wsum) || 4.0 * emax > rel * (double)mp) { good = false; break; }
+                std::vector<size_t> ord(mag.size());
+                for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
+                std::sort(ord.begin(), ord.end(), [&](size_t a, size_t bb) { return mag[a] < mag[bb]; });
+                unsigned long long cum = b.outside;
+                med[3 * j + p] = (double)mp;
+                for (size_t k = 0; k < ord.size(); k++) { cum += b.v[ord[k]].w; if (rank < cum) { med[3 * j + p] = mag[ord[k]]; break; } }
+            }
+            if (good) done.push_back(j); else again.push_back(j);
+        }
+        todo.swap(again);
+    }
+    // capacities: thr = magmin * med, window 1e-3 widened x4, at most 4 rounds (tfft_capacity); a plane with thr <= 0 counts every annulus bin
+    const CapParams cp = cap_params(c, s, rmin, rmax);
+    P.cap = 1; P.s_lo = cp.s_lo; P.s_hi = cp.s_hi;
+    std::vector<unsigned long long> exact_u(u);
+    todo.clear();
+    for (int j : done) {
+        if (cp.bw > 0) todo.push_back(j);
+        else { exact_u[sel[j]] = 0; state[sel[j]] = 1; }      // an empty annulus holds nothing
+    }
+    rel = 1e-3;
+    for (int attempt = 0; attempt < 4 && !todo.empty(); attempt++, rel *= 4.0) {
+        std::vector<ExactWin> win(todo.size());
+        for (size_t z = 0; z < todo.size(); z++) {
+            win[z].img = todo[z];
+            for (int p = 0; p < 3; p++) {
+                const double thr = magmin * med[3 * todo[z] + p];
+                if (thr > 0.0) exact_window(thr, rel, win[z].lo2[p], win[z].hi2[p]);
+                else win[z].lo2[p] = win[z].hi2[p] = -1.f;      // every |F|^2 lies above: the count is the annulus
+            }
+        }
+        std::vector<BxList> o;
+        rc = bx_round(c, s0, src, img_bytes, P, win, o, &max_cand, st);
+        if (rc) return rc;
+        cap_rounds++;
+        std::vector<int> again;
+        for (size_t z = 0; z < todo.size(); z++) {
+            const int j = todo[z];
+            if (!o[3 * z].ok) continue;
+            bool good = true;
+            unsigned long long total = 0;
+            for (int p = 0; p < 3 && good; p++) {
+                const BxList& b = o[3 * z + p];
+                const double thr = magmin * med[3 * j + p];
+                unsigned long long cnt = b.outside;
+                double emax = 0.0;
+                for (const ExactVal& v : b.v) {
+                    const double mag = hypot(v.re, v.im);
+                    emax = fmax(emax, fabs(mag - sqrt((double)v.m2)));
+                    if (!(mag < thr)) cnt += v.w;                            // S:1004
+                }
+                if (4.0 * emax > rel * thr) good = false;
+                total += cnt / 2;                                            // S:1007
+            }
+            if (good) { exact_u[sel[j]] = total; state[sel[j]] = 1; }
+            else again.push_back(j);
+        }
+        todo.swap(again);
+    }
+    if (c->bx_trace)
+        fprintf(stderr, "tfft batch exact: %d of %d images settled, %d median + %d capacity rounds, max %u candidates per plane\n",
+                (int)std::count(state, state + g, 1), g, med_rounds, cap_rounds, max_cand);
+    HIPCHK(c, hipMemcpyAsync(usable, exact_u.data(), (size_t)g * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));                 // (exact_u is a host array)
+    return TFFT_OK;
+}
+// the state array of a batched embed call (nullptr without usable_out: the states of the last call that filled one stay)
+int32_t* bx_begin(tfft_ctx* c, int n_images, const void* usable) {
+    if (!usable || n_images < 0) return nullptr;
+    c->bx_state.assign((size_t)n_images, 0);
+    c->bx_last_n = n_images;
+    return c->bx_state.data();
+}
+// the covers of a chunk whose embed writes over them (rgb_out overlaps rgb): copied to the slots' image pool first
+const uint8_t* bx_keep_covers(tfft_ctx* c, int g, const uint8_t* rgb, const uint8_t* rgb_out, size_t img_bytes, hipStream_t st, int* rc) {
+    *rc = TFFT_OK;
+    const size_t len = (size_t)g * img_bytes;
+    if (rgb_out + len <= rgb || rgb + len <= rgb_out) return rgb;
+    if (hipMemcpyAsync(c->img(0), rgb, len, hipMemcpyDeviceToDevice, st) != hipSuccess) { *rc = TFFT_E_HIP; return rgb; }
+    return c->img(0);
+}
 }  // namespace
 
 int tfft_medians(tfft_ctx* c, int slot, double med[3]) {
@@ -997,6 +1257,23 @@ int tfft_set_phase_options(tfft_ctx* c, const float* jitter, uint64_t n, int ada
     }
     HIPCHK(c, hipMemcpy(c->ph_jit, jitter, n * sizeof(float), hipMemcpyHostToDevice));
     c->ph_n = n;
+    return TFFT_OK;
+}
+
+int tfft_set_batch_exact(tfft_ctx* c, int mode, uint64_t guard_bits) {
+    if (!c || mode < TFFT_BATCH_EXACT_OFF || mode > TFFT_BATCH_EXACT_NEAR) return TFFT_E_INVALID;
+    if (mode != TFFT_BATCH_EXACT_OFF) {
+        HIPCHK(c, hipSetDevice(c->device));
+        int rc = bx_buffers(c);
+        if (rc) return rc;
+    }
+    c->bx_mode = mode; c->bx_guard = guard_bits;
+    return TFFT_OK;
+}
+
+int tfft_batch_exact_info(const tfft_ctx* c, int n_images, int32_t* state_out) {
+    if (!c || n_images < 0 || n_images > c->bx_last_n || (n_images && !state_out)) return TFFT_E_INVALID;
+    for (int i = 0; i < n_images; i++) state_out[i] = c->bx_state[i];
     return TFFT_OK;
 }
 
@@ -1544,12 +1821,14 @@ static int split_join(tfft_ctx* c) {
 
 static int embed_batch_dev_impl(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, const void* bins_dev,
                                 const void* bits_dev, uint64_t n_bits, double alpha, double rmin, double rmax, double magmin,
-                                void* usable_out_dev, void* rgb_out_dev) {
+                                void* usable_out_dev, void* rgb_out_dev, int32_t* bx = nullptr) {
     const size_t img_bytes = (size_t)w * h * 3;
     for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
         const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
         int rc = batch_geometry(c, g, w, h, center);
         if (rc) return rc;
+        const uint8_t* cov = (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes;
+        if (bx && c->bx_mode) { cov = bx_keep_covers(c, g, cov, (const uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes, img_bytes, c->stream, &rc); if (rc) return rc; }
         int h1 = 0;
         rc = split_fork(c, g, &h1);
         if (rc) return rc;
@@ -1562,6 +1841,7 @@ static int embed_batch_dev_impl(tfft_ctx* c, int n_images, const void* rgb_dev, 
             if (rc) return rc;
         }
         if (h1) { rc = split_join(c); if (rc) return rc; }
+        if (bx) { rc = bx_settle(c, 0, g, cov, rmin, rmax, magmin, n_bits, (unsigned long long*)usable_out_dev + i0, bx + i0, c->stream); if (rc) return rc; }
     }
     return TFFT_OK;
 }
@@ -1580,6 +1860,9 @@ int tfft_embed_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, 
                          void* usable_out_dev, void* rgb_out_dev) {
     if (!c || n_images < 0 || !rgb_dev || !rgb_out_dev || (n_bits && (!bins_dev || !bits_dev))) return TFFT_E_INVALID;
     if (!index_ok(c, n_bits) || !phase_ok(c, n_bits)) return TFFT_E_STATE;
+    int32_t* bx = bx_begin(c, n_images, usable_out_dev);
+    if (bx && c->bx_mode)      // (settling synchronises: never captured or replayed)
+        return embed_batch_dev_impl(c, n_images, rgb_dev, w, h, center, bins_dev, bits_dev, n_bits, alpha, rmin, rmax, magmin, usable_out_dev, rgb_out_dev, bx);
     std::vector<uint64_t> key = {1, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), key_bits(bits_dev),
                                        n_bits, key_bits(alpha), key_bits(rmin), key_bits(rmax), key_bits(magmin), key_bits(usable_out_dev),
                                        key_bits(rgb_out_dev), key_bits(c->bit_index), key_bits((double)c->dc_bias)};
@@ -1642,7 +1925,7 @@ static int ensure_stream(tfft_ctx* c, uint64_t n_bins) {
 
 static int embed_stream_batch_dev_impl(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, const void* bins_dev,
                                        uint64_t n_bins, const void* header_dev, const void* payload_dev, uint64_t payload_len, double alpha,
-                                       double rmin, double rmax, double magmin, void* usable_out_dev, void* rgb_out_dev) {
+                                       double rmin, double rmax, double magmin, void* usable_out_dev, void* rgb_out_dev, int32_t* bx = nullptr) {
     const uint64_t n_bits = 38ull * 24 + payload_len * 56;           // S:986-995
     int rc = TFFT_OK;
     const size_t img_bytes = (size_t)w * h * 3;
@@ -1650,12 +1933,15 @@ static int embed_stream_batch_dev_impl(tfft_ctx* c, int n_images, const void* rg
         const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
         rc = batch_geometry(c, g, w, h, center);
         if (rc) return rc;
+        const uint8_t* cov = (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes;
+        if (bx && c->bx_mode) { cov = bx_keep_covers(c, g, cov, (const uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes, img_bytes, c->stream, &rc); if (rc) return rc; }
         // bits_from_bytes + rep3/rep7_encode happen inside k_embed: every bin computes its own stream bit from the packed frame
         const FrameSrc fr{(const uint8_t*)header_dev + (size_t)i0 * 38, (const uint8_t*)payload_dev + (size_t)i0 * payload_len, payload_len};
         rc = embed_chunk(c, 0, g, (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, (const tfft_bin*)bins_dev, nullptr, n_bins, alpha, rmin, rmax,
                          magmin, usable_out_dev ? (unsigned long long*)usable_out_dev + i0 : nullptr, (uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes,
                          c->stream, n_bits, &fr);
         if (rc) return rc;
+        if (bx) { rc = bx_settle(c, 0, g, cov, rmin, rmax, magmin, n_bits, (unsigned long long*)usable_out_dev + i0, bx + i0, c->stream); if (rc) return rc; }
     }
     return TFFT_OK;
 }
@@ -1670,6 +1956,10 @@ int tfft_embed_stream_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, 
     if (!index_ok(c, n_bins) || !phase_ok(c, n_bins)) return TFFT_E_STATE;
     int rc = ensure_stream(c, n_bins);                                // (may reallocate: before any cached sequence is looked up)
     if (rc) return rc;
+    int32_t* bx = bx_begin(c, n_images, usable_out_dev);
+    if (bx && c->bx_mode)      // (settling synchronises: never captured or replayed)
+        return embed_stream_batch_dev_impl(c, n_images, rgb_dev, w, h, center, bins_dev, n_bins, header_dev, payload_dev, payload_len, alpha,
+                                           rmin, rmax, magmin, usable_out_dev, rgb_out_dev, bx);
     std::vector<uint64_t> key = {3, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), n_bins,
                                        key_bits(header_dev), key_bits(payload_dev), payload_len, key_bits(alpha), key_bits(rmin), key_bits(rmax),
                                        key_bits(magmin), key_bits(usable_out_dev), key_bits(rgb_out_dev), key_bits(c->bit_index), key_bits((double)c->dc_bias)};
@@ -1760,6 +2050,7 @@ static int batch_host(tfft_ctx* c, bool embed, int n_images, const uint8_t* rgb,
                       const tfft_bin* bins, const uint8_t* bits, uint64_t n_bits, double alpha, double rmin, double rmax,
                       double magmin, uint64_t* usable, uint8_t* rgb_out, uint8_t* bits_out, const StreamIO* sio = nullptr,
                       const WalkSrc* walks = nullptr) {
+    int32_t* bx = embed ? bx_begin(c, n_images, usable) : nullptr;
     if (n_images == 0) return TFFT_OK;
     int rc = pipe_init(c);
     if (rc) return rc;
@@ -1810,11 +2101,13 @@ static int batch_host(tfft_ctx* c, bool embed, int n_images, const uint8_t* rgb,
             limit = 38ull * 24 + sio->plen * 56;
             fr = FrameSrc{c->sio_hdr + (size_t)s0 * 38, c->sio_pay + (size_t)s0 * sio->plen, sio->plen};
         }
-        if (embed)
+        if (embed) {
             rc = embed_chunk(c, s0, g, c->img(s0), d_bins, sio ? nullptr : d_bits, n_bits, alpha, rmin, rmax, magmin,
                              usable ? c->usable + s0 : nullptr, c->out_pool + (size_t)s0 * c->img_stride_b, c->stream, limit, sio ? &fr : nullptr,
                              walks ? &wpart : nullptr);   // packed, like the input
-        else
+            if (!rc && bx)      // (the part's covers stay in its image buffers until ev_comp)
+                rc = bx_settle(c, s0, g, c->img(s0), rmin, rmax, magmin, sio ? limit : n_bits, c->usable + s0, bx + i0, c->stream);
+        } else
             rc = extract_chunk(c, s0, g, c->img(s0), d_bins, n_bits, alpha, d_bout, c->stream, walks ? &wpart : nullptr);
         if (rc) return rc;
         if (!embed && sio)       // header -> clen -> payload on the device: only packed bytes and a status word go back
@@ -1888,10 +2181,13 @@ int tfft_embed_stream_batch_walks_dev(tfft_ctx* c, int n_images, const void* rgb
     if (n_bins < 912 || payload_len > (n_bins - 912) / 56) return TFFT_E_INVALID;      // (before the multiplication: a huge length must not wrap)
     const uint64_t n_bits = 38ull * 24 + payload_len * 56;           // S:986-995
     const size_t img_bytes = (size_t)w * h * 3;
+    int32_t* bx = bx_begin(c, n_images, usable_out_dev);
     for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
         const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
         rc = batch_geometry(c, g, w, h, center);
         if (rc) return rc;
+        const uint8_t* cov = (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes;
+        if (bx && c->bx_mode) { cov = bx_keep_covers(c, g, cov, (const uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes, img_bytes, c->stream, &rc); if (rc) return rc; }
         int h1 = 0;
         rc = split_fork(c, g, &h1);
         if (rc) return rc;
@@ -1905,6 +2201,7 @@ int tfft_embed_stream_batch_walks_dev(tfft_ctx* c, int n_images, const void* rgb
             if (rc) return rc;
         }
         if (h1) { rc = split_join(c); if (rc) return rc; }
+        if (bx) { rc = bx_settle(c, 0, g, cov, rmin, rmax, magmin, n_bits, (unsigned long long*)usable_out_dev + i0, bx + i0, c->stream); if (rc) return rc; }
     }
     return n_images ? check_err_flag(c) : TFFT_OK;
 }
@@ -2081,6 +2378,7 @@ int tfft_embed_stream_batch_fit_dev(tfft_ctx* c, int n_images, const void* rgb_d
     const uint64_t n_bits = 38ull * 24 + payload_len * 56;           // S:986-995
     const size_t img_bytes = (size_t)w * h * 3;
     std::vector<int32_t> iters((size_t)c->n_slots);
+    int32_t* bx = bx_begin(c, n_images, usable_out_dev);
     for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
         const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
         rc = batch_geometry(c, g, w, h, center);
@@ -2092,6 +2390,7 @@ int tfft_embed_stream_batch_fit_dev(tfft_ctx* c, int n_images, const void* rgb_d
                        n_bins, adaptive, fr, n_bits, alpha, rmin, rmax, magmin, usable_out_dev ? (unsigned long long*)usable_out_dev + i0 : nullptr,
                        max_iters, margin, (uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes, iters.data(), wrong_out_dev ? (uint32_t*)wrong_out_dev + i0 : nullptr);
         if (rc) return rc;
+        if (bx) { rc = bx_settle(c, 0, g, c->img(0), rmin, rmax, magmin, n_bits, (unsigned long long*)usable_out_dev + i0, bx + i0, c->stream); if (rc) return rc; }
         if (iters_out_dev) {
             HIPCHK(c, hipMemcpyAsync((int32_t*)iters_out_dev + i0, iters.data(), (size_t)g * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));      // (the host array is reused by the next chunk)
@@ -2116,6 +2415,7 @@ int tfft_embed_stream_batch_fit(tfft_ctx* c, int n_images, const uint8_t* rgb, i
     const uint64_t n_bits = 38ull * 24 + payload_len * 56;
     const size_t img_bytes = (size_t)w * h * 3;
     std::vector<int32_t> iters((size_t)c->n_slots);
+    int32_t* bx = bx_begin(c, n_images, usable_out);
     hipStream_t st = c->stream;
     for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
         const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
@@ -2130,6 +2430,7 @@ int tfft_embed_stream_batch_fit(tfft_ctx* c, int n_images, const uint8_t* rgb, i
         rc = fit_chunk(c, g, c->img(0), (const tfft_bin*)c->stage_bins, jitter ? (const float*)c->stage_jit : nullptr, n_bins, adaptive, fr, n_bits,
                        alpha, rmin, rmax, magmin, usable_out ? c->usable : nullptr, max_iters, margin, c->out_pool, iters.data(), c->fit_wrong);
         if (rc) return rc;
+        if (bx) { rc = bx_settle(c, 0, g, c->img(0), rmin, rmax, magmin, n_bits, c->usable, bx + i0, st); if (rc) return rc; }
         HIPCHK(c, hipMemcpyAsync(rgb_out + (size_t)i0 * img_bytes, c->out_pool, (size_t)g * img_bytes, hipMemcpyDeviceToHost, st));
         if (usable_out) HIPCHK(c, hipMemcpyAsync(usable_out + i0, c->usable, (size_t)g * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         if (wrong_out) HIPCHK(c, hipMemcpyAsync(wrong_out + i0, c->fit_wrong, (size_t)g * sizeof(uint32_t), hipMemcpyDeviceToHost, st));

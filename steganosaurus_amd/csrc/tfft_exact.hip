@@ -13,7 +13,8 @@
 //
 // Cost: one more pass over the stored spectrum + a few dozen 256-thread workgroups per candidate walking the image (L2 resident):
 // a fraction of a millisecond for a 1080p image, a few host round trips.  That is why it serves the single-image calls (tfft_medians / tfft_capacity: what the CLI uses
-// for "Message too large") and not the batched pipelines, whose statistics stay on the fp32 planes.
+// for "Message too large").  The batched pipelines keep their fp32 statistics unless tfft_set_batch_exact asks for the reference's integer:
+// then the batched kernels below settle a whole chunk of images per launch.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -138,6 +139,173 @@ __global__ void __launch_bounds__(256) k_exact_eval(const uint8_t* __restrict__ 
         __syncthreads();
     }
     if (tid == 0) out[(size_t)blockIdx.x * gridDim.y + blockIdx.y] = red[0];
+}
+
+// ---- batched form (tfft_set_batch_exact): the chunk of a batched embed, each image with its own windows
+// k_exact_collect over n_win images of one geometry (grid.z = launch entry z, image win[z].img of the stored spectra): the same rules,
+// per-image windows read from device memory, counters and candidate lists per (entry, plane)
+__global__ void k_exact_collect_batch(const float2* __restrict__ spec, size_t img_stride, ExactCollect P, const ExactWin* __restrict__ win,
+                                      ExactCandB* __restrict__ cand, unsigned long long* __restrict__ below, unsigned* __restrict__ n_cand) {
+    const int plane = blockIdx.y, z = blockIdx.z, M = P.PW >> 1, l = 3 * z + plane;
+    const int img = win[z].img;
+    const float2* pl = spec + (size_t)img * img_stride + (size_t)plane * P.PH * M;
+    const float lo2 = win[z].lo2[plane], hi2 = win[z].hi2[plane];
+    ExactCandB* out = cand + (size_t)l * P.cap_cand;
+    unsigned long long acc = 0;
+    auto emit = [&](int y, int x, unsigned w, float m2) {
+        const unsigned slot = atomicAdd(&n_cand[l], 1u);
+        if (slot < (unsigned)P.cap_cand) {
+            ExactCandB e; e.y = (uint16_t)y; e.x = (uint16_t)x; e.w = (uint16_t)w; e.plane = (uint16_t)plane; e.m2 = m2; e.img = (uint32_t)img; out[slot] = e;
+        }
+    };
+    for (int y = blockIdx.x; y < P.PH; y += gridDim.x) {
+        for (int x = threadIdx.x; x < M; x += blockDim.x) {
+            if (x == 0) {
+                if (P.cap) continue;
+                float2 f0, fm;
+                exact_unpack_col0(pl, y, P.PH, M, f0, fm);
+                const float a = fmaf(f0.x, f0.x, f0.y * f0.y), b = fmaf(fm.x, fm.x, fm.y * fm.y);
+                if (a < lo2) acc += 1; else if (a <= hi2) emit(y, 0, 1u, a);
+                if (b < lo2) acc += 1; else if (b <= hi2) emit(y, M, 1u, b);
+                continue;
+            }
+            const float2 v = pl[(size_t)y * M + x];
+            const float m2 = fmaf(v.x, v.x, v.y * v.y);
+            if (!P.cap) {
+                if (m2 < lo2) acc += 2; else if (m2 <= hi2) emit(y, x, 2u, m2);
+            } else {
+                unsigned w = 0;
+                if (y != 0 && 2 * y != P.PH) {
+                    const unsigned long long d1 = (unsigned long long)y * y + (unsigned long long)x * x;
+                    w = (d1 >= P.s_lo && d1 <= P.s_hi) ? 1u : 0u;
+                    const unsigned long long ym = (unsigned long long)(P.PH - y), xm = (unsigned long long)(P.PW_full - x);
+                    const unsigned long long d2 = ym * ym + xm * xm;
+                    w += (d2 >= P.s_lo && d2 <= P.s_hi) ? 1u : 0u;
+                }
+                if (!w) continue;
+                if (m2 > hi2) acc += w; else if (m2 >= lo2) emit(y, x, w, m2);
+            }
+        }
+    }
+    unsigned long long* red = reinterpret_cast<unsigned long long*>(tfft_smem);
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = blockDim.x >> 1; s > 0; s >>= 1) { if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s]; __syncthreads(); }
+    if (threadIdx.x == 0 && red[0]) atomicAdd(&below[l], red[0]);
+}
+
+// k_exact_eval for up to K candidates of one (image, plane) at once: the workgroup walks its row band of the plane once and every pixel
+// load feeds K sums.  Per candidate the arithmetic is k_exact_eval's, operation for operation: thread tid owns the same pixels (rows
+// r0 + tid/16 step 16, columns tid%16 step 16), the fma chain per row, the row factor, the accumulation into tre/tim and the 256-wide LDS
+// tree are the same, so every partial -- and after the in-order sum, every magnitude -- equals the single-image value bit for bit.
+//   grid (n_groups, n_split); LDS max(PW, K*256) double2 (the table, then the K reduction trees)
+template <int K>
+__global__ void __launch_bounds__(256) k_exact_eval_batch(const uint8_t* __restrict__ rgb, size_t img_bytes, int W, int H, int PW, int PH, int center,
+                                                           const ExactCandB* __restrict__ cand, const unsigned* __restrict__ idx,
+                                                           const ExactGroup* __restrict__ groups, const double2* __restrict__ table,
+                                                           double2* __restrict__ out) {
+    double2* T = reinterpret_cast<double2*>(tfft_smem);
+    const ExactGroup gr = groups[blockIdx.x];
+    const int tid = threadIdx.x, rr = tid >> 4, cc = tid & 15;
+    for (int j = tid; j < PW; j += 256) T[j] = table[j];
+    const unsigned pmask = (unsigned)(PW - 1);
+    unsigned xe[K], ye[K];
+    int plane = 0;
+    uint32_t img = 0;
+#pragma unroll
+    for (int k = 0; k < K; k++) {      // (a short group repeats its last candidate; those sums are not written)
+        const ExactCandB cd = cand[idx[gr.first + (k < (int)gr.count ? k : (int)gr.count - 1)]];
+        xe[k] = ((unsigned)cd.x + (center ? (unsigned)(PW >> 1) : 0u)) & pmask;
+        ye[k] = ((unsigned)cd.y + (center ? (unsigned)(PH >> 1) : 0u)) & (unsigned)(PH - 1);
+        plane = cd.plane; img = cd.img;
+    }
+    __syncthreads();
+    const uint8_t* base = rgb + (size_t)img * img_bytes + plane;
+    const int rows_per = (H + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int r0 = blockIdx.y * rows_per, r1 = (r0 + rows_per < H) ? r0 + rows_per : H;
+    double tre[K], tim[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) { tre[k] = 0.0; tim[k] = 0.0; }
+    for (int r = r0 + rr; r < r1; r += 16) {
+        const uint8_t* row = base + (size_t)r * W * 3;
+        double are[K], aim[K];
+        unsigned id[K], step[K];
+#pragma unroll
+        for (int k = 0; k < K; k++) { are[k] = 0.0; aim[k] = 0.0; id[k] = (xe[k] * (unsigned)cc) & pmask; step[k] = (xe[k] * 16u) & pmask; }
+        for (int c = cc; c < W; c += 16) {
+            const double p = (double)row[3 * c];
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const double2 w = T[id[k]];
+                are[k] = fma(p, w.x, are[k]); aim[k] = fma(p, w.y, aim[k]);
+                id[k] = (id[k] + step[k]) & pmask;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            double s, c;
+            sincospi(2.0 * (double)((ye[k] * (unsigned)r) & (unsigned)(PH - 1)) / (double)PH, &s, &c);
+            tre[k] += are[k] * c - aim[k] * s;
+            tim[k] += are[k] * s + aim[k] * c;
+        }
+    }
+    __syncthreads();                    // the table is dead: its space carries the K reduction trees
+    double2* red = reinterpret_cast<double2*>(tfft_smem);
+#pragma unroll
+    for (int k = 0; k < K; k++) red[k * 256 + tid] = make_double2(tre[k], tim[k]);
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) {
+#pragma unroll
+            for (int k = 0; k < K; k++) { red[k * 256 + tid].x += red[k * 256 + tid + s].x; red[k * 256 + tid].y += red[k * 256 + tid + s].y; }
+        }
+        __syncthreads();
+    }
+    if (tid < (int)gr.count) out[(size_t)(gr.first + tid) * gridDim.y + blockIdx.y] = red[tid * 256];
+}
+
+// the partials of each dense candidate added in split order (exact_round's host loop, the same fp64 additions)
+__global__ void k_exact_sum_batch(const double2* __restrict__ part, int n_split, const ExactCandB* __restrict__ cand, const unsigned* __restrict__ idx,
+                                  unsigned n, ExactVal* __restrict__ out) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double re = 0.0, im = 0.0;
+    for (int k = 0; k < n_split; k++) { re += part[(size_t)i * n_split + k].x; im += part[(size_t)i * n_split + k].y; }
+    const ExactCandB cd = cand[idx[i]];
+    ExactVal v; v.re = re; v.im = im; v.m2 = cd.m2; v.w = cd.w;
+    out[i] = v;
+}
+
+hipError_t launch_exact_collect_batch(const float2* spec, size_t img_stride, const ExactCollect& P, const ExactWin* win, int n_win, ExactCandB* cand,
+                                      unsigned long long* below, unsigned* n_cand, hipStream_t s) {
+    if (n_win <= 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(below, 0, (size_t)3 * n_win * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(n_cand, 0, (size_t)3 * n_win * sizeof(unsigned), s);
+    if (e != hipSuccess) return e;
+    int nb = P.PH < 1024 ? P.PH : 1024;
+    hipLaunchKernelGGL(k_exact_collect_batch, dim3(nb, 3, n_win), dim3(256), 256 * sizeof(unsigned long long), s, spec, img_stride, P, win, cand, below, n_cand);
+    return hipGetLastError();
+}
+
+hipError_t launch_exact_eval_batch(const uint8_t* rgb, size_t img_bytes, int W, int H, int PW, int PH, int center, const ExactCandB* cand,
+                                   const unsigned* idx, const ExactGroup* groups, unsigned n_groups, int n_split, const double2* table, double2* out, hipStream_t s) {
+    if (n_groups == 0) return hipSuccess;
+    const size_t lds = (size_t)(PW > 256 * TFFT_EXACT_K ? PW : 256 * TFFT_EXACT_K) * sizeof(double2);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)k_exact_eval_batch<TFFT_EXACT_K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_exact_eval_batch<TFFT_EXACT_K>, dim3(n_groups, n_split), dim3(256), lds, s, rgb, img_bytes, W, H, PW, PH, center, cand, idx, groups,
+                       table, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_exact_sum_batch(const double2* part, int n_split, const ExactCandB* cand, const unsigned* idx, unsigned n, ExactVal* out, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_exact_sum_batch, dim3((n + 255) / 256), dim3(256), 0, s, part, n_split, cand, idx, n, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_exact_collect(const float2* spec, const ExactCollect& P, ExactCand* cand, unsigned long long* below, unsigned* n_cand, hipStream_t s) {

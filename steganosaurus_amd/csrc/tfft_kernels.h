@@ -144,6 +144,20 @@ hipError_t launch_exact_collect(const float2* spec, const ExactCollect& P, Exact
 hipError_t launch_exact_table(double2* table, int PW, hipStream_t s);
 hipError_t launch_exact_eval(const uint8_t* rgb, int W, int H, int PW, int PH, int center, const ExactCand* cand, unsigned n, int n_split,
                              const double2* table, double2* out, hipStream_t s);
+// ... and their batched form (tfft_set_batch_exact): many images of one geometry per launch, each with its own windows
+struct ExactCandB { uint16_t y, x, w, plane; float m2; uint32_t img; };      // ExactCand + the image (index into the launch's covers / spectra)
+struct ExactWin { int img; float lo2[3], hi2[3]; int rsv; };                 // collect launch entry z: which image, its per-plane |F|^2 windows
+struct ExactVal { double re, im; float m2; uint32_t w; };                    // a settled candidate: fp64 F (partials added in order), fp32 |F|^2, weight
+struct ExactGroup { unsigned first, count; };                                  // k_exact_eval_batch workgroup: dense candidates [first, first + count)
+#define TFFT_EXACT_K 8                // candidates of one (image, plane) per k_exact_eval_batch workgroup: one pixel load serves all of them
+// grid (rows, 3, n_win): candidates of entry z, plane p at cand + (3z+p)*P.cap_cand, counters at below / n_cand [3z+p]
+hipError_t launch_exact_collect_batch(const float2* spec, size_t img_stride, const ExactCollect& P, const ExactWin* win, int n_win, ExactCandB* cand,
+                                      unsigned long long* below, unsigned* n_cand, hipStream_t s);
+// groups: n_groups x (first dense index, count 1..TFFT_EXACT_K) into idx[] (-> cand[]), all of one (image, plane); out = n_dense * n_split partials
+hipError_t launch_exact_eval_batch(const uint8_t* rgb, size_t img_bytes, int W, int H, int PW, int PH, int center, const ExactCandB* cand,
+                                   const unsigned* idx, const ExactGroup* groups, unsigned n_groups, int n_split, const double2* table, double2* out, hipStream_t s);
+// out[i] = the n_split partials of dense candidate i added in order (as the single-image host loop adds them) + its m2 and weight
+hipError_t launch_exact_sum_batch(const double2* part, int n_split, const ExactCandB* cand, const unsigned* idx, unsigned n, ExactVal* out, hipStream_t s);
 
 #define TFFT_STAT_MAX_BLOCKS 512
 
