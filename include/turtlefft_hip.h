@@ -311,6 +311,34 @@ int tfft_embed_stream_batch_fit(tfft_ctx* ctx, int n_images, const uint8_t* rgb,
  * The quantiser + SHA-256 of the hash stay with the caller (libtfhost: tfh_cover_hash_from_mags). */
 int tfft_lowfreq_mag_batch_dev(tfft_ctx* ctx, int n_images, const void* rgb_dev, int w, int h, int center, int region, void* out_dev);
 
+/* ------------------------------------------------------------ stego analysis
+ * What a stego batch gives away, measured on the device (the phase-histogram detector and the PSNR / SSIM of the reference's security
+ * analysis).  Per image and plane: a histogram of the phases of the annulus bins of the image's padded spectrum -- the bins count_plane
+ * (S:998-1008) counts: full-plane unshifted (y, x), y != 0, x != 0, 2y != PH, 2x != PW, rmin*mn <= hypot(y, x) <= rmax*mn, and
+ * |F| >= thr[plane] under the capacity kernels' fp32 test (thr == NULL: no magnitude test).
+ * theta = atan2(Im F, Re F) of the full-plane coefficient in the reference's sign convention (the angle read_bit_from_bin, S:736, takes);
+ * for x > PW/2 that is minus the angle of the stored mirror.  bin = floor((theta + pi) * n_hist_bins / (2 pi)) mod n_hist_bins (theta = +-pi
+ * both land in bin 0).  hist_out: uint32, image i plane p at (i*3 + p)*n_hist_bins.  n_hist_bins: a power of two in [8, 4096].
+ * Needs no bin list or medians, and ignores the bit index, the registered list and the phase options.  Overwrites the slots' spectra, as a
+ * batch call does (tfft_lowfreq_mag then gives TFFT_E_STATE).  The _dev form does not synchronise (but for growing its scratch on first
+ * use); the host form stages one chunk of n_slots images at a time and synchronises. */
+int tfft_phase_hist_batch_dev(tfft_ctx* ctx, int n_images, const void* rgb_dev, int w, int h, int center, double rmin, double rmax,
+                              const double thr[3] /* or NULL */, int n_hist_bins, void* hist_out_dev);
+int tfft_phase_hist_batch(tfft_ctx* ctx, int n_images, const uint8_t* rgb, int w, int h, int center, double rmin, double rmax,
+                          const double thr[3] /* or NULL */, int n_hist_bins, uint32_t* hist_out);
+/* a, b: n_images RGB8 images of w x h (image i at + i*w*h*3).  sse_out: uint64 per image and plane, sum of (a - b)^2, exact.
+ * ssim_out (double per image and plane, or NULL): mean SSIM of the plane (Wang et al. 2004): 11 x 11 Gaussian window, sigma 1.5,
+ * normalised to sum 1; K1 = 0.01, K2 = 0.03, L = 255; population moments (E[x^2] - mu^2, evaluated on pixel - 128 in fp32, the window means
+ * added in fp64 in a fixed order); mean over the (W-10)(H-10) windows that lie inside the image; exactly 1.0 for a plane whose SSE is 0.
+ * ssim_out with w < 11 or h < 11: TFFT_E_INVALID; w > max_w or h > max_h: TFFT_E_TOO_LARGE.  Leaves the slots alone (spectra and
+ * image buffers: tfft_medians, tfft_capacity and tfft_lowfreq_mag of a resident image answer as before the call).
+ * Deterministic: repeated calls return identical bytes.  PSNR = 10 log10(255^2 W H / SSE) per plane, +inf when SSE = 0 (the caller's).
+ * The host form stages chunks in buffers of its own and synchronises. */
+int tfft_quality_batch_dev(tfft_ctx* ctx, int n_images, const void* a_dev, const void* b_dev, int w, int h,
+                           void* sse_out_dev, void* ssim_out_dev /* or NULL */);
+int tfft_quality_batch(tfft_ctx* ctx, int n_images, const uint8_t* a, const uint8_t* b, int w, int h,
+                       uint64_t* sse_out, double* ssim_out /* or NULL */);
+
 /* --------------------------------------------------------- keyed walk (HOST)
  * KS + Turtle + the density gate (S:665-695, S:749-810, S:1076-1081): a
  * resumable generator of embedding positions.  Pure host code, no device.

@@ -85,6 +85,10 @@ SYMBOLS = {
     "tfft_embed_stream_batch_fit": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _u64, _i, _vp, _vp, _u64, _d, _d, _d, _d, _i, _d,
                                          _vp, _vp, _vp, _vp]),
     "tfft_walks_build": (_i, [_i, _vp, _i, _i, _d, _d, _d, _d, _u64, _i, _vp, _vp, _vp]),
+    "tfft_phase_hist_batch_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _d, _d, _vp, _i, _vp]),
+    "tfft_phase_hist_batch": (_i, [_vp, _i, _vp, _i, _i, _i, _d, _d, _vp, _i, _vp]),
+    "tfft_quality_batch_dev": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "tfft_quality_batch": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "tfft_profile_stage": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _u64, _d, C.POINTER(C.c_float), _pi]),
     "tfft_timer_begin": (_i, [_vp]),
     "tfft_timer_end": (_i, [_vp, C.POINTER(C.c_float)]),
@@ -457,6 +461,39 @@ class Context:
         """compute_cover_hash's magnitudes of n images: out = n*3*region*region doubles (device)"""
         _check(self.lib.tfft_lowfreq_mag_batch_dev(self.h, n_images, _ptr(rgb_ptr), w, h, int(center), region, _ptr(out_ptr)),
                "tfft_lowfreq_mag_batch_dev")
+
+    # ---- stego analysis (DESIGN.md section 12) ----------------------------------------------------------------------
+    def phase_hist_batch_dev(self, n_images, rgb_ptr, w, h, hist_out_ptr, nbins=256, center=False, rmin=0.05, rmax=0.45, thr=None):
+        """annulus phase histograms of n images (device): hist_out = n*3*nbins uint32; thr: 3 magnitude thresholds or None"""
+        t = None if thr is None else np.ascontiguousarray(thr, np.float64)
+        _check(self.lib.tfft_phase_hist_batch_dev(self.h, n_images, _ptr(rgb_ptr), w, h, int(center), rmin, rmax, _ptr(t), int(nbins),
+                                                  _ptr(hist_out_ptr)), "tfft_phase_hist_batch_dev")
+
+    def phase_hist_batch_host(self, rgb, nbins=256, center=False, rmin=0.05, rmax=0.45, thr=None):
+        """rgb: (n,H,W,3) uint8 host array -> (n, 3, nbins) uint32"""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        n, h, w = rgb.shape[:3]
+        out = np.zeros((n, 3, nbins), np.uint32)
+        t = None if thr is None else np.ascontiguousarray(thr, np.float64)
+        _check(self.lib.tfft_phase_hist_batch(self.h, n, _ptr(rgb), w, h, int(center), rmin, rmax, _ptr(t), int(nbins), _ptr(out)),
+               "tfft_phase_hist_batch")
+        return out
+
+    def quality_batch_dev(self, n_images, a_ptr, b_ptr, w, h, sse_out_ptr, ssim_out_ptr=None):
+        """SSE (n*3 uint64) and mean SSIM (n*3 float64, optional) of n image pairs (device)"""
+        _check(self.lib.tfft_quality_batch_dev(self.h, n_images, _ptr(a_ptr), _ptr(b_ptr), w, h, _ptr(sse_out_ptr), _ptr(ssim_out_ptr)),
+               "tfft_quality_batch_dev")
+
+    def quality_batch_host(self, a, b, ssim=True):
+        """a, b: (n,H,W,3) uint8 host arrays -> (sse (n,3) uint64, ssim (n,3) float64 or None)"""
+        a = np.ascontiguousarray(a, np.uint8)
+        b = np.ascontiguousarray(b, np.uint8)
+        assert a.shape == b.shape
+        n, h, w = a.shape[:3]
+        sse = np.zeros((n, 3), np.uint64)
+        out = np.zeros((n, 3), np.float64) if ssim else None
+        _check(self.lib.tfft_quality_batch(self.h, n, _ptr(a), _ptr(b), w, h, _ptr(sse), _ptr(out)), "tfft_quality_batch")
+        return sse, out
 
     STAGES = ["rows_fwd", "cols_fwd_a", "cols_fwd_b", "embed", "cols_inv_a", "cols_inv_b", "rows_inv", "read",
               "medians", "capacity", "cols_fwd_read"]

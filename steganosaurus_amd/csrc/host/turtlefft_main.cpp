@@ -33,6 +33,7 @@ struct Params {     // S:375-381
     bool adaptive_alpha = false;
     bool cover_dependent_path = false;
     bool fit_crop = false;          // embed only, not in the reference: fit the stego so that it survives the crop to W x H
+    bool report = false;            // embed only, not in the reference: PSNR / SSIM / phase-histogram KL of the written stego on stderr
 };
 struct Args {       // S:839-845
     std::string mode, inPath, outPath, secret, pass, keyBase64, keyOutPath, wrapPass;
@@ -49,6 +50,7 @@ void usage() {
             "      [--alpha 0.5 --jitter 0 --density 0.7 --rmin 0.05 --rmax 0.45 --magmin 0.01 --center 0]\n"
             "      [--pbkdf2_iter 600000 --adaptive_alpha 0 --cover_dependent_path 0 --wrap-pass PW]\n"
             "      [--fit_crop 0]  1: fit the stego so that covers whose sides are not powers of two read back\n"
+            "      [--report 0]    1: print PSNR, SSIM and the annulus phase-histogram KL(stego||cover) per plane on stderr\n"
             "  turtlefft extract --in stego.png (--pass PW | --key KEY_BASE64)\n"
             "      [same tuning options as embed]\n"
             "  The 2-D FFT / phase embedding runs on an AMD MI355X through libturtlefft_hip.so.\n");
@@ -83,6 +85,7 @@ const OptSpec kOptions[] = {
     {"--adaptive_alpha", OptKind::Flag, nullptr, nullptr, &Params::adaptive_alpha, nullptr},
     {"--cover_dependent_path", OptKind::Flag, nullptr, nullptr, &Params::cover_dependent_path, nullptr},
     {"--fit_crop", OptKind::Flag, nullptr, nullptr, &Params::fit_crop, nullptr},
+    {"--report", OptKind::Flag, nullptr, nullptr, &Params::report, nullptr},
     {"--pbkdf2_iter", OptKind::Count, nullptr, nullptr, nullptr, &Params::pbkdf2_iter},
 };
 
@@ -175,6 +178,46 @@ void open_image(const Args& A, Spectrum& S, const std::vector<uint8_t>& rgb, boo
     turtle_subkeys(S.path_key, S.sub);
 }
 
+// --report 1: one line on stderr comparing the cover with the bytes just written -- PSNR and SSIM per plane (tfft_quality_batch) and
+// KL(stego || cover) of the 256-bin annulus phase histograms (tfft_phase_hist_batch, no magnitude test), smoothed as
+// steganosaurus_amd.analysis.kl_divergence: P = (c + 0.5) / (N + 0.5 nb), natural log
+void report_line(const Args& A, Spectrum& S, const std::vector<uint8_t>& cover, const std::vector<uint8_t>& stego) {
+    constexpr int NB = 256;
+    const bool ssim_ok = S.W >= 11 && S.H >= 11;
+    uint64_t sse[3];
+    double ssim[3];
+    tf(tfft_quality_batch(S.ctx, 1, cover.data(), stego.data(), S.W, S.H, sse, ssim_ok ? ssim : nullptr), "report");
+    std::vector<uint32_t> hc(3 * NB), hs(3 * NB);
+    tf(tfft_phase_hist_batch(S.ctx, 1, cover.data(), S.W, S.H, A.P.center, A.P.rmin, A.P.rmax, nullptr, NB, hc.data()), "report");
+    tf(tfft_phase_hist_batch(S.ctx, 1, stego.data(), S.W, S.H, A.P.center, A.P.rmin, A.P.rmax, nullptr, NB, hs.data()), "report");
+    std::string line = "Report: PSNR(dB)";
+    char buf[64];
+    const char* names[3] = {"R", "G", "B"};
+    for (int p = 0; p < 3; p++) {
+        if (sse[p] == 0) snprintf(buf, sizeof buf, " %s=inf", names[p]);
+        else snprintf(buf, sizeof buf, " %s=%.6f", names[p], 10.0 * log10(255.0 * 255.0 * (double)S.W * (double)S.H / (double)sse[p]));
+        line += buf;
+    }
+    line += "; SSIM";
+    for (int p = 0; p < 3; p++) {
+        if (ssim_ok) snprintf(buf, sizeof buf, " %s=%.6f", names[p], ssim[p]);
+        else snprintf(buf, sizeof buf, " %s=n/a", names[p]);
+        line += buf;
+    }
+    line += "; KL(stego||cover)";
+    for (int p = 0; p < 3; p++) {
+        double np_ = 0.0, nq = 0.0, kl = 0.0;
+        for (int i = 0; i < NB; i++) { np_ += hs[p * NB + i]; nq += hc[p * NB + i]; }
+        for (int i = 0; i < NB; i++) {
+            const double P = (hs[p * NB + i] + 0.5) / (np_ + 0.5 * NB), Q = (hc[p * NB + i] + 0.5) / (nq + 0.5 * NB);
+            kl += P * log(P / Q);
+        }
+        snprintf(buf, sizeof buf, " %s=%.8f", names[p], kl);
+        line += buf;
+    }
+    fprintf(stderr, "%s\n", line.c_str());
+}
+
 void do_embed(const Args& A) {      // S:907-1109
     const bool using_raw_key = !A.keyBase64.empty();
     std::array<uint8_t, 32> master_key{};
@@ -184,7 +227,7 @@ void do_embed(const Args& A) {      // S:907-1109
     if (using_raw_key && !decode_or_unwrap_key(A.keyBase64, A.wrapPass, A.P.pbkdf2_iter, master_key))
         die("Failed to decode/unwrap key from --key argument");
     open_image(A, S, rgb, using_raw_key, master_key);
-    if (!A.P.fit_crop) std::vector<uint8_t>().swap(rgb);      // (the fitted embed adds to the cover again and again)
+    if (!A.P.fit_crop && !A.P.report) std::vector<uint8_t>().swap(rgb);      // (the fitted embed adds to the cover again and again; the report compares)
 
     std::array<uint8_t, 16> salt{};
     { std::random_device rd; for (auto& b : salt) b = (uint8_t)rd(); }                  // S:927-929
@@ -230,6 +273,7 @@ void do_embed(const Args& A) {      // S:907-1109
     if (!png_write_rgb8(A.outPath, out.data(), S.W, S.H)) die("PNG write failed: %s", A.outPath.c_str());
     fprintf(stdout, "Embedded %zu bits into %s (payload %u bytes, ver=2, salt/nonce in header)\n", bits.size(),
             A.outPath.c_str(), (unsigned)A.secret.size());
+    if (A.P.report) report_line(A, S, rgb, out);
 }
 
 void do_extract(const Args& A) {    // S:1112-1312

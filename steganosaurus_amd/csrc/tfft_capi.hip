@@ -152,6 +152,8 @@ struct tfft_ctx {
     std::vector<int32_t> bx_state; int bx_last_n = 0;
     ExactWin* bx_win = nullptr; ExactCandB* bx_cand = nullptr; unsigned long long* bx_below = nullptr; unsigned* bx_n = nullptr;
     unsigned* bx_idx = nullptr; ExactGroup* bx_grp = nullptr; double2* bx_part = nullptr; ExactVal* bx_val = nullptr; size_t bx_part_cap = 0, bx_val_cap = 0;
+    // stego analysis (tfft_phase_hist_batch*, tfft_quality_batch*): per-block partials of a chunk (+ the host forms' results), grown on demand
+    void* an_buf = nullptr; size_t an_cap = 0;
 
     uint8_t* img(int i) const { return img_pool + (size_t)i * img_stride_b; }
     float2* spec(int i) const { return spec_pool + (size_t)i * slot_stride; }
@@ -667,7 +669,7 @@ int tfft_destroy(tfft_ctx* c) {
     (void)hipFree(c->sel); (void)hipFree(c->med); (void)hipFree(c->partial); (void)hipFree(c->amb); (void)hipFree(c->usable); (void)hipFree(c->err); (void)hipFree(c->ex_cand); (void)hipFree(c->ex_val); (void)hipFree(c->ex_below); (void)hipFree(c->ex_n); for (auto& kv : c->ex_table) (void)hipFree(kv.second); (void)hipFree(c->trash); (void)hipFree(c->bit_index); (void)hipFree(c->last_row); (void)hipFree(c->ph_jit);
     (void)hipFree(c->fit_d); (void)hipFree(c->fit_mu); (void)hipFree(c->fit_part); (void)hipFree(c->fit_cnt); (void)hipFree(c->fit_iters); (void)hipFree(c->fit_wrong);
     (void)hipFree(c->bx_win); (void)hipFree(c->bx_cand); (void)hipFree(c->bx_below); (void)hipFree(c->bx_n); (void)hipFree(c->bx_idx); (void)hipFree(c->bx_grp);
-    (void)hipFree(c->bx_part); (void)hipFree(c->bx_val);
+    (void)hipFree(c->bx_part); (void)hipFree(c->bx_val); (void)hipFree(c->an_buf);
     for (auto& b : c->tb) { (void)hipFree(b.cnt); (void)hipFree(b.off); (void)hipFree(b.ent); (void)hipFree(b.fl); (void)hipFree(b.pb); (void)hipFree(b.jp); }
     for (auto& kv : c->tw) (void)hipFree(kv.second);
     for (auto& kv : c->dc) (void)hipFree(kv.second);
@@ -2456,6 +2458,164 @@ int tfft_lowfreq_mag_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, i
         HIPCHK(c, launch_lowfreq_f64_batch((const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, s.W, s.H, s.PW, s.PH, s.center, region, g,
                                            (double2*)c->tmp(0), c->slot_stride * sizeof(float2) / sizeof(double2), (double*)out_dev + (size_t)i0 * out_len,
                                            c->stream));
+    }
+    return TFFT_OK;
+}
+
+// ---- stego analysis: annulus phase histograms, cover / stego quality
+}  // extern "C"
+namespace {
+// the analysis scratch (partials of one chunk, then the host forms' results): grown on demand; an earlier call may still read it
+int ensure_analysis(tfft_ctx* c, size_t bytes) {
+    if (c->an_buf && bytes <= c->an_cap) return TFFT_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(c->an_buf); c->an_buf = nullptr; c->an_cap = 0;
+    const size_t cap = bytes + bytes / 4 + 4096;
+    int rc = dev_alloc(c, &c->an_buf, cap);
+    if (rc) return rc;
+    c->an_cap = cap;
+    return TFFT_OK;
+}
+
+int phase_hist_args(tfft_ctx* c, int n_images, const void* rgb, int w, int h, int center, int n_hist_bins, const void* out, int* log_bins) {
+    if (!c || n_images < 1 || !rgb || !out || n_hist_bins < 8 || n_hist_bins > 4096 || (n_hist_bins & (n_hist_bins - 1))) return TFFT_E_INVALID;
+    Slot s;
+    int rc = set_geometry(c, s, w, h, center);
+    if (rc) return rc;
+    *log_bins = ilog2i(n_hist_bins);
+    return TFFT_OK;
+}
+
+// g images (device, packed) -> storing forward into slots [0, g) -> histograms to hist (device, 3*nbins words per image); extra: bytes
+// of the scratch the caller keeps after the partials
+int phase_hist_chunk(tfft_ctx* c, int g, const uint8_t* rgb, int w, int h, int center, double rmin, double rmax, const double thr[3], int log_bins,
+                     size_t extra, uint32_t** hist) {
+    int rc = batch_geometry(c, g, w, h, center);
+    if (rc) return rc;
+    PhaseHistParams P{};
+    P.cap = cap_params(c, c->slots[0], rmin, rmax);
+    for (int q = 0; q < 3; q++) P.t2[q] = thr ? mag2_threshold(thr[q]) : -INFINITY;
+    P.log_bins = log_bins;
+    const size_t part = ((size_t)g * 3 * phase_hist_blocks(P.cap, log_bins, g) << log_bins) * sizeof(unsigned);
+    rc = ensure_analysis(c, part + extra);
+    if (rc) return rc;
+    if (!*hist) *hist = (uint32_t*)((char*)c->an_buf + part);
+    rc = enqueue_forward(c, 0, g, rgb, c->stream);      // the storing forward: complex values are needed, not |F|^2
+    if (rc) return rc;
+    HIPCHK(c, launch_phase_hist(c->spec(0), P, g, (unsigned*)c->an_buf, *hist, c->stream));
+    return TFFT_OK;
+}
+
+int quality_args(const tfft_ctx* c, int n_images, const void* a, const void* b, int w, int h, const void* sse, const void* ssim) {
+    if (!c || n_images < 1 || !a || !b || !sse || w < 1 || h < 1) return TFFT_E_INVALID;
+    if (w > c->max_w || h > c->max_h) return TFFT_E_TOO_LARGE;
+    if (ssim && (w < 11 || h < 11)) return TFFT_E_INVALID;
+    return TFFT_OK;
+}
+
+QualityParams quality_params(int w, int h) {
+    QualityParams P{};
+    P.W = w; P.H = h;
+    double g[11], sum = 0.0;
+    for (int k = 0; k < 11; k++) { g[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5)); sum += g[k]; }
+    for (int k = 0; k < 11; k++) P.g[k] = (float)(g[k] / sum);
+    return P;
+}
+
+// the partials of a chunk of g pairs, at the start of the analysis scratch (SSE then SSIM per (image, plane, tile))
+size_t quality_part_bytes(int g, const QualityParams& P) {
+    return (size_t)g * 3 * quality_partials(P.W, P.H) * (sizeof(unsigned long long) + sizeof(double));
+}
+
+// g image pairs (device, packed) -> sse / ssim (device, 3 per image; ssim may be nullptr).  The caller has sized the scratch
+// (ensure_analysis of at least quality_part_bytes(g, P))
+int quality_chunk(tfft_ctx* c, int g, const uint8_t* a, const uint8_t* b, const QualityParams& P, unsigned long long* sse, double* ssim) {
+    const size_t nt = (size_t)g * 3 * quality_partials(P.W, P.H);
+    unsigned long long* sse_part = (unsigned long long*)c->an_buf;
+    double* ssim_part = (double*)(sse_part + nt);
+    HIPCHK(c, launch_quality(a, b, P, g, sse_part, ssim_part, sse, ssim, c->stream));
+    return TFFT_OK;
+}
+}  // namespace
+extern "C" {
+
+int tfft_phase_hist_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, double rmin, double rmax,
+                              const double thr[3], int n_hist_bins, void* hist_out_dev) {
+    int lb = 0;
+    int rc = phase_hist_args(c, n_images, rgb_dev, w, h, center, n_hist_bins, hist_out_dev, &lb);
+    if (rc) return rc;
+    const size_t img_bytes = (size_t)w * h * 3, hist_len = (size_t)3 << lb;
+    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
+        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+        uint32_t* hist = (uint32_t*)hist_out_dev + (size_t)i0 * hist_len;
+        rc = phase_hist_chunk(c, g, (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, w, h, center, rmin, rmax, thr, lb, 0, &hist);
+        if (rc) return rc;
+    }
+    return TFFT_OK;
+}
+
+int tfft_phase_hist_batch(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int h, int center, double rmin, double rmax,
+                          const double thr[3], int n_hist_bins, uint32_t* hist_out) {
+    int lb = 0;
+    int rc = phase_hist_args(c, n_images, rgb, w, h, center, n_hist_bins, hist_out, &lb);
+    if (rc) return rc;
+    const size_t img_bytes = (size_t)w * h * 3, hist_len = (size_t)3 << lb;
+    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
+        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+        for (int i = 0; i < g; i++) { c->slots[i].has_spec = false; c->slots[i].rgb_src = nullptr; }      // their images go now (the forward follows)
+        HIPCHK(c, hipMemcpyAsync(c->img(0), rgb + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, c->stream));
+        uint32_t* hist = nullptr;
+        rc = phase_hist_chunk(c, g, c->img(0), w, h, center, rmin, rmax, thr, lb, (size_t)g * hist_len * sizeof(uint32_t), &hist);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(hist_out + (size_t)i0 * hist_len, hist, (size_t)g * hist_len * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return TFFT_OK;
+}
+
+int tfft_quality_batch_dev(tfft_ctx* c, int n_images, const void* a_dev, const void* b_dev, int w, int h, void* sse_out_dev, void* ssim_out_dev) {
+    int rc = quality_args(c, n_images, a_dev, b_dev, w, h, sse_out_dev, ssim_out_dev);
+    if (rc) return rc;
+    const QualityParams P = quality_params(w, h);
+    const size_t img_bytes = (size_t)w * h * 3;
+    rc = ensure_analysis(c, quality_part_bytes(n_images < c->n_slots ? n_images : c->n_slots, P));
+    if (rc) return rc;
+    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
+        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+        rc = quality_chunk(c, g, (const uint8_t*)a_dev + (size_t)i0 * img_bytes, (const uint8_t*)b_dev + (size_t)i0 * img_bytes, P,
+                           (unsigned long long*)sse_out_dev + (size_t)i0 * 3, ssim_out_dev ? (double*)ssim_out_dev + (size_t)i0 * 3 : nullptr);
+        if (rc) return rc;
+    }
+    return TFFT_OK;
+}
+
+// host buffers: a chunk of n_slots pairs at a time, staged OUTSIDE the slots' image buffers (which tfft_lowfreq_mag and the exact statistics
+// read again after a single-image forward): the second images in the staging pool of the host pipelines, the first ones in the analysis
+// scratch behind the partials and the chunk's results
+int tfft_quality_batch(tfft_ctx* c, int n_images, const uint8_t* a, const uint8_t* b, int w, int h, uint64_t* sse_out, double* ssim_out) {
+    int rc = quality_args(c, n_images, a, b, w, h, sse_out, ssim_out);
+    if (rc) return rc;
+    rc = pipe_init(c);
+    if (rc) return rc;
+    const QualityParams P = quality_params(w, h);
+    const size_t img_bytes = (size_t)w * h * 3;
+    const int g0 = n_images < c->n_slots ? n_images : c->n_slots;
+    const size_t part = quality_part_bytes(g0, P), res = (size_t)g0 * 3 * (sizeof(unsigned long long) + sizeof(double));
+    const size_t stage_off = (part + res + 255) / 256 * 256;
+    rc = ensure_analysis(c, stage_off + (size_t)g0 * img_bytes);
+    if (rc) return rc;
+    unsigned long long* sse = (unsigned long long*)((char*)c->an_buf + part);
+    double* ssim = (double*)(sse + (size_t)g0 * 3);
+    uint8_t* a_stage = (uint8_t*)c->an_buf + stage_off;
+    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
+        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+        HIPCHK(c, hipMemcpyAsync(a_stage, a + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->out_pool, b + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, c->stream));
+        rc = quality_chunk(c, g, a_stage, c->out_pool, P, sse, ssim_out ? ssim : nullptr);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(sse_out + (size_t)i0 * 3, sse, (size_t)g * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        if (ssim_out) HIPCHK(c, hipMemcpyAsync(ssim_out + (size_t)i0 * 3, ssim, (size_t)g * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return TFFT_OK;
 }

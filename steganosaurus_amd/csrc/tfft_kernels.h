@@ -259,4 +259,28 @@ hipError_t launch_lowfreq_f64(const uint8_t* rgb, int W, int H, int PW, int PH, 
 hipError_t launch_lowfreq_f64_batch(const uint8_t* rgb, int W, int H, int PW, int PH, int center, int region, int n_images, double2* rowsum,
                                     size_t rowsum_stride, double* out, hipStream_t s);
 
+// ---- stego analysis
+// annulus phase histograms of n_images resident spectra (img_stride apart): hist_out[(img*3 + plane)*nbins + bin], uint32
+struct PhaseHistParams {
+    CapParams cap;          // the annulus box, its exact radius bounds and img_stride (cap_params; thr / magmin unused)
+    float t2[3];            // per plane: bins with |F|^2 < t2 are not counted (mag2_threshold(thr); -inf: no magnitude test)
+    int log_bins;           // nbins = 1 << log_bins, 3..12
+};
+#define TFFT_PH_PARTIAL_WORDS 65536      // partial-histogram words per (image, plane) at most (blocks x nbins)
+int phase_hist_blocks(const CapParams& cp, int log_bins, int n_images);      // partial = n_images*3*blocks*nbins words
+hipError_t launch_phase_hist(const float2* spec, const PhaseHistParams& P, int n_images, unsigned* partial, uint32_t* hist_out, hipStream_t s);
+// cover / stego quality of n_images image pairs (W*H*3 bytes apart): sse_out, ssim_out (or nullptr) per (image, plane);
+// partials: n_images*3*quality_partials(W, H) of each kind
+#define TFFT_QA_TX 64                    // window positions per tile (columns x rows)
+#define TFFT_QA_TY 32
+#define TFFT_QA_LDS_OFF 18656            // both images' bytes of a tile + halo, 3 planes: 2*3*(TY+10)*(TX+10), rounded up to 16
+#define TFFT_QA_LDS (TFFT_QA_LDS_OFF + 5 * (TFFT_QA_TY + 10) * TFFT_QA_TX * 4)      // + the horizontal pass's five moments, fp32
+#define TFFT_QA_C1 6.5025f               // (K1 L)^2, K1 = 0.01, L = 255
+#define TFFT_QA_C2 58.5225f              // (K2 L)^2, K2 = 0.03
+static_assert(TFFT_QA_LDS_OFF >= 2 * 3 * (TFFT_QA_TY + 10) * (TFFT_QA_TX + 10) && TFFT_QA_LDS_OFF % 16 == 0, "quality tile bytes");
+struct QualityParams { int W, H; float g[11]; };      // g: the 11-tap Gaussian (sigma 1.5), normalised to sum 1
+size_t quality_partials(int W, int H);
+hipError_t launch_quality(const uint8_t* a, const uint8_t* b, const QualityParams& P, int n_images, unsigned long long* sse_part, double* ssim_part,
+                          unsigned long long* sse_out, double* ssim_out, hipStream_t s);
+
 }  // namespace tfft

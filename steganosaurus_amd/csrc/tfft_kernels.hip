@@ -3417,4 +3417,264 @@ hipError_t launch_lowfreq_f64_batch(const uint8_t* rgb, int W, int H, int PW, in
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// stego analysis
+// ---------------------------------------------------------------------------
+// Annulus phase histograms: the bins count_plane (S:998-1008) counts -- the box and the exact integer radius test of k_capacity, its
+// fp32 magnitude test -- binned by theta = atan2(Im F, Re F) of the FULL-plane coefficient (x > M: the conjugate of the stored mirror).
+// Each wave counts into its own copy of the histogram in LDS while there is room for four (fewer LDS atomics on the same word); the
+// block writes one partial histogram and k_phase_hist_sum adds the NB partials of a bin in block order (integers: no order effects).
+//   grid (NB, 3, n_images)  block 256  LDS copies * nbins words   partial[((img*3 + plane)*NB + block)*nbins + bin]
+__device__ __forceinline__ int phase_bin(float im, float re, double scale, int nbins) {
+    const double t = ((double)atan2f(im, re) + 3.14159265358979323846) * scale;      // (theta + pi) * nbins / (2 pi)
+    int b = (int)floor(t);
+    if (b < 0) b = 0;                    // theta = -pi in fp32 lies a hair below -pi: bin 0, as theta = +pi (b = nbins) is
+    return b & (nbins - 1);
+}
+template <bool WIDE>
+__global__ void __launch_bounds__(256) k_phase_hist(const float2* __restrict__ spec, PhaseHistParams P, unsigned* __restrict__ partial) {
+    unsigned* hist = reinterpret_cast<unsigned*>(tfft_smem);
+    const int nbins = 1 << P.log_bins;
+    const int copies = P.log_bins >= 12 ? 1 : (P.log_bins == 11 ? 2 : 4);
+    for (int i = threadIdx.x; i < copies * nbins; i += blockDim.x) hist[i] = 0;
+    __syncthreads();
+    unsigned* h = hist + (int)((threadIdx.x >> 6) % (unsigned)copies) * nbins;
+    const int plane = blockIdx.y, img = blockIdx.z;
+    const CapParams& cp = P.cap;
+    const float t2 = P.t2[plane];
+    const double scale = (double)nbins * 0.15915494309189533577;      // nbins / (2 pi)
+    const int M = cp.PWi >> 1;
+    const float2* pl = spec + (size_t)img * cp.img_stride + (size_t)plane * cp.PH * M;
+    typedef typename std::conditional<WIDE, unsigned long long, unsigned>::type R;
+    const R s_lo = (R)cp.s_lo, s_hi = (R)cp.s_hi;
+    for (int y = blockIdx.x; y < cp.bh; y += gridDim.x) {
+        if (y == 0 || 2 * y == cp.PH) continue;
+        const R yy = (R)y * (R)y;
+        const float2* row = pl + (size_t)y * M;                                  // bins x < M
+        const float2* mrow = pl + (size_t)((cp.PH - y) & (cp.PH - 1)) * M;         // bins x > M: conj of (PH-y, PW-x)
+        for (int x0 = threadIdx.x; x0 < cp.bw; x0 += 4 * blockDim.x) {
+            float2 v[4]; bool in[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int x = x0 + u * (int)blockDim.x;
+                const R s = yy + (R)x * (R)x;
+                in[u] = x < cp.bw && x != 0 && 2 * x != cp.PW && s >= s_lo && s <= s_hi;
+                v[u] = in[u] ? (x < M ? row[x] : cconj(mrow[cp.PW - x])) : make_float2(0.f, 0.f);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (in[u] && !(mag2_of(v[u]) < t2)) atomicAdd(&h[phase_bin(v[u].y, v[u].x, scale, nbins)], 1u);
+        }
+    }
+    __syncthreads();
+    unsigned* out = partial + (((size_t)img * 3 + plane) * gridDim.x + blockIdx.x) * (size_t)nbins;
+    for (int i = threadIdx.x; i < nbins; i += blockDim.x) {
+        unsigned s = 0;
+        for (int c = 0; c < copies; c++) s += hist[c * nbins + i];
+        out[i] = s;
+    }
+}
+//   grid (ceil(nbins/256), 3*n_images)  block 256: hist[z*nbins + i] = sum over blocks b of partial[(z*nb + b)*nbins + i]
+__global__ void __launch_bounds__(256) k_phase_hist_sum(const unsigned* __restrict__ partial, int nb, int nbins, uint32_t* __restrict__ hist) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, z = blockIdx.y;
+    if (i >= nbins) return;
+    const unsigned* p = partial + (size_t)z * nb * nbins + i;
+    unsigned s = 0;
+    for (int b = 0; b < nb; b++) s += p[(size_t)b * nbins];
+    hist[(size_t)z * nbins + i] = s;
+}
+
+// Cover / stego quality: per tile of TFFT_QA_TX x TFFT_QA_TY window positions, both images' bytes of the tile and its 10-pixel halo in LDS (all three
+// planes), then per plane the separable 11-tap Gaussian of the five moments of x = a - 128, y = b - 128 (x, y, x^2, y^2, xy): the
+// horizontal pass writes them to LDS (a thread filters 8 adjacent columns of one row, every pixel's products formed once), the vertical
+// pass keeps 8 outputs of one column in registers.  SSE over the tile's own pixels in integers; the SSIM of the tile's windows added in
+// fp64.  Partials per (image, plane, tile); k_quality_sum adds them in a fixed order.
+//   grid (ceil(W/TFFT_QA_TX), ceil(H/TFFT_QA_TY), n_images)  block 256
+template <bool SSIM>
+__global__ void __launch_bounds__(256) k_quality(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, QualityParams P,
+                                                 unsigned long long* __restrict__ sse_part, double* __restrict__ ssim_part) {
+    constexpr int RX = TFFT_QA_TX + 10, RY = TFFT_QA_TY + 10, PLN = RY * RX;
+    uint8_t* la = reinterpret_cast<uint8_t*>(tfft_smem);                      // [3][RY][RX]
+    uint8_t* lb = la + 3 * PLN;                                               // [3][RY][RX]
+    float* hs = reinterpret_cast<float*>(tfft_smem + TFFT_QA_LDS_OFF);       // [5][RY][TFFT_QA_TX]
+    // block sums: after the filters over the moments (SSIM), at the start of the LDS otherwise (SSE only: no tile is kept)
+    constexpr size_t RED_OFF = SSIM ? TFFT_QA_LDS_OFF : 0;
+    unsigned long long* red = reinterpret_cast<unsigned long long*>(tfft_smem + RED_OFF);                          // [3][256]
+    double* redd = reinterpret_cast<double*>(tfft_smem + RED_OFF + 3 * 256 * sizeof(unsigned long long));     // [3][256], SSIM only
+    const int tid = threadIdx.x, img = blockIdx.z;
+    const int x0 = blockIdx.x * TFFT_QA_TX, y0 = blockIdx.y * TFFT_QA_TY;
+    const size_t img_bytes = (size_t)P.W * P.H * 3;
+    const uint8_t* ia = a + (size_t)img * img_bytes;
+    const uint8_t* ib = b + (size_t)img * img_bytes;
+    // load the tile + halo (zeros outside the image) into LDS; SSE of the tile's own pixels.  SSE only: just the own pixels, no LDS
+    unsigned long long sse[3] = {0, 0, 0};
+    const int rx = (P.W - x0 < RX ? P.W - x0 : RX), ry = (P.H - y0 < RY ? P.H - y0 : RY);
+    const int own_x = (P.W - x0 < TFFT_QA_TX ? P.W - x0 : TFFT_QA_TX), own_y = (P.H - y0 < TFFT_QA_TY ? P.H - y0 : TFFT_QA_TY);
+    constexpr int LX = SSIM ? RX : TFFT_QA_TX, LY = SSIM ? RY : TFFT_QA_TY;
+    for (int e = tid; e < LY * 3 * LX; e += blockDim.x) {
+        const int r = e / (3 * LX), k = e - r * 3 * LX, c = k / 3, p = k - 3 * c;
+        uint8_t va = 0, vb = 0;
+        if (r < (SSIM ? ry : own_y) && c < (SSIM ? rx : own_x)) {
+            const size_t o = ((size_t)(y0 + r) * P.W + (x0 + c)) * 3 + p;
+            va = ia[o]; vb = ib[o];
+            if (r < own_y && c < own_x) { const int d = (int)va - (int)vb; sse[p] += (unsigned)(d * d); }
+        }
+        if (SSIM) { la[p * PLN + r * RX + c] = va; lb[p * PLN + r * RX + c] = vb; }
+    }
+    double ssum[3] = {0.0, 0.0, 0.0};
+    if (SSIM) {
+        __syncthreads();
+        const int nwx = P.W - 10 - x0, nwy = P.H - 10 - y0;                     // window positions of this tile: x < nwx, y < nwy
+        for (int p = 0; p < 3; p++) {
+            // horizontal: item (row r, columns 8*cg .. 8*cg+7)
+            for (int it = tid; it < RY * (TFFT_QA_TX / 8); it += blockDim.x) {
+                const int r = it / (TFFT_QA_TX / 8), c0 = (it - r * (TFFT_QA_TX / 8)) * 8;
+                float acc[8][5];
+#pragma unroll
+                for (int j = 0; j < 8; j++)
+#pragma unroll
+                    for (int m = 0; m < 5; m++) acc[j][m] = 0.f;
+                const uint8_t* pa = la + p * PLN + r * RX + c0;
+                const uint8_t* pb = lb + p * PLN + r * RX + c0;
+#pragma unroll
+                for (int i = 0; i < 18; i++) {
+                    const float x = (float)((int)pa[i] - 128), y = (float)((int)pb[i] - 128);
+                    const float v[5] = {x, y, x * x, y * y, x * y};
+#pragma unroll
+                    for (int j = 0; j < 8; j++) {
+                        if (i - j < 0 || i - j > 10) continue;
+#pragma unroll
+                        for (int m = 0; m < 5; m++) acc[j][m] = fmaf(P.g[i - j], v[m], acc[j][m]);
+                    }
+                }
+#pragma unroll
+                for (int m = 0; m < 5; m++)
+#pragma unroll
+                    for (int j = 0; j < 8; j++) hs[(m * RY + r) * TFFT_QA_TX + c0 + j] = acc[j][m];
+            }
+            __syncthreads();
+            // vertical: item (column c, output rows 8*rg .. 8*rg+7)
+            for (int it = tid; it < TFFT_QA_TX * (TFFT_QA_TY / 8); it += blockDim.x) {
+                const int c = it % TFFT_QA_TX, r0 = (it / TFFT_QA_TX) * 8;
+                float acc[8][5];
+#pragma unroll
+                for (int j = 0; j < 8; j++)
+#pragma unroll
+                    for (int m = 0; m < 5; m++) acc[j][m] = 0.f;
+#pragma unroll
+                for (int i = 0; i < 18; i++) {
+                    float v[5];
+#pragma unroll
+                    for (int m = 0; m < 5; m++) v[m] = hs[(m * RY + r0 + i) * TFFT_QA_TX + c];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) {
+                        if (i - j < 0 || i - j > 10) continue;
+#pragma unroll
+                        for (int m = 0; m < 5; m++) acc[j][m] = fmaf(P.g[i - j], v[m], acc[j][m]);
+                    }
+                }
+                if (c < nwx) {
+#pragma unroll
+                    for (int j = 0; j < 8; j++) {
+                        if (r0 + j >= nwy) continue;
+                        const float mx = acc[j][0] + 128.f, my = acc[j][1] + 128.f;      // the means of the pixels themselves
+                        const float sx = acc[j][2] - acc[j][0] * acc[j][0], sy = acc[j][3] - acc[j][1] * acc[j][1];
+                        const float sxy = acc[j][4] - acc[j][0] * acc[j][1];
+                        const float num = (2.f * mx * my + TFFT_QA_C1) * (2.f * sxy + TFFT_QA_C2);
+                        const float den = (mx * mx + my * my + TFFT_QA_C1) * (sx + sy + TFFT_QA_C2);
+                        ssum[p] += (double)(num / den);
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    } else {
+        __syncthreads();
+    }
+    // block sums in a fixed order
+    for (int p = 0; p < 3; p++) { red[p * 256 + tid] = sse[p]; if (SSIM) redd[p * 256 + tid] = ssum[p]; }
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s)
+            for (int p = 0; p < 3; p++) { red[p * 256 + tid] += red[p * 256 + tid + s]; if (SSIM) redd[p * 256 + tid] += redd[p * 256 + tid + s]; }
+        __syncthreads();
+    }
+    if (tid < 3) {
+        const size_t ntiles = (size_t)gridDim.x * gridDim.y, t = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+        sse_part[((size_t)img * 3 + tid) * ntiles + t] = red[tid * 256];
+        if (SSIM) ssim_part[((size_t)img * 3 + tid) * ntiles + t] = redd[tid * 256];
+    }
+}
+//   grid (3*n_images)  block 256: the tiles' partials of (image, plane) z added in a fixed order; SSIM = sum / windows, 1 where SSE = 0
+__global__ void __launch_bounds__(256) k_quality_sum(const unsigned long long* __restrict__ sse_part, const double* __restrict__ ssim_part,
+                                                     int ntiles, double n_windows, unsigned long long* __restrict__ sse_out, double* __restrict__ ssim_out) {
+    unsigned long long* red = reinterpret_cast<unsigned long long*>(tfft_smem);
+    double* redd = reinterpret_cast<double*>(tfft_smem + 256 * sizeof(unsigned long long));
+    const int tid = threadIdx.x, z = blockIdx.x;
+    unsigned long long s = 0; double d = 0.0;
+    for (int t = tid; t < ntiles; t += blockDim.x) { s += sse_part[(size_t)z * ntiles + t]; if (ssim_out) d += ssim_part[(size_t)z * ntiles + t]; }
+    red[tid] = s; redd[tid] = d;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (tid < k) { red[tid] += red[tid + k]; redd[tid] += redd[tid + k]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        sse_out[z] = red[0];
+        if (ssim_out) ssim_out[z] = red[0] == 0 ? 1.0 : redd[0] / n_windows;
+    }
+}
+
+int phase_hist_blocks(const CapParams& cp, int log_bins, int n_images) {
+    // rows of the box per block: about a dozen as k_capacity, more when the flush of the partial histogram would cost more than an
+    // eighth of the block's reads; at least ~1024 blocks per launch, and at most TFFT_PH_PARTIAL_WORDS partial words per plane
+    const int nbins = 1 << log_bins, bh = cp.bh > 0 ? cp.bh : 1, bw = cp.bw > 0 ? cp.bw : 1;
+    int rows = (4 * nbins + bw - 1) / bw;
+    if (rows < 12) rows = 12;
+    int nb = (bh + rows - 1) / rows;
+    const int fill = (1024 + 3 * n_images - 1) / (3 * n_images);
+    if (nb < fill) nb = fill;
+    if (nb > bh) nb = bh;
+    if (nb > TFFT_STAT_MAX_BLOCKS) nb = TFFT_STAT_MAX_BLOCKS;
+    if (nb > TFFT_PH_PARTIAL_WORDS / nbins) nb = TFFT_PH_PARTIAL_WORDS / nbins;
+    return nb < 1 ? 1 : nb;
+}
+
+hipError_t launch_phase_hist(const float2* spec, const PhaseHistParams& P, int n_images, unsigned* partial, uint32_t* hist_out, hipStream_t s) {
+    if (P.log_bins < 3 || P.log_bins > 12 || n_images < 1 || n_images > 65535) return hipErrorInvalidValue;
+    const int nbins = 1 << P.log_bins, nb = phase_hist_blocks(P.cap, P.log_bins, n_images);
+    const int copies = P.log_bins >= 12 ? 1 : (P.log_bins == 11 ? 2 : 4);
+    const size_t lds = (size_t)copies * nbins * sizeof(unsigned);
+    const CapParams& cp = P.cap;
+    const bool wide = cp.PH > 32768 || cp.PW > 32768 || cp.s_hi > 0xFFFFFFFFull || cp.s_lo > 0xFFFFFFFFull;
+    if (wide) hipLaunchKernelGGL(k_phase_hist<true>, dim3(nb, 3, n_images), dim3(256), lds, s, spec, P, partial);
+    else hipLaunchKernelGGL(k_phase_hist<false>, dim3(nb, 3, n_images), dim3(256), lds, s, spec, P, partial);
+    hipLaunchKernelGGL(k_phase_hist_sum, dim3((nbins + 255) / 256, 3 * n_images), dim3(256), 0, s, partial, nb, nbins, hist_out);
+    return hipGetLastError();
+}
+
+size_t quality_partials(int W, int H) {
+    return (size_t)((W + TFFT_QA_TX - 1) / TFFT_QA_TX) * (size_t)((H + TFFT_QA_TY - 1) / TFFT_QA_TY);
+}
+
+hipError_t launch_quality(const uint8_t* a, const uint8_t* b, const QualityParams& P, int n_images, unsigned long long* sse_part, double* ssim_part,
+                          unsigned long long* sse_out, double* ssim_out, hipStream_t s) {
+    if (P.W < 1 || P.H < 1 || n_images < 1 || n_images > 65535 || (ssim_out && (P.W < 11 || P.H < 11))) return hipErrorInvalidValue;
+    const unsigned tx = (unsigned)((P.W + TFFT_QA_TX - 1) / TFFT_QA_TX), ty = (unsigned)((P.H + TFFT_QA_TY - 1) / TFFT_QA_TY);
+    if (ty > 65535) return hipErrorInvalidValue;
+    const size_t lds = TFFT_QA_LDS;
+    if (ssim_out) {
+        hipError_t e = hipFuncSetAttribute((const void*)k_quality<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_quality<true>, dim3(tx, ty, n_images), dim3(256), lds, s, a, b, P, sse_part, ssim_part);
+    } else {
+        hipLaunchKernelGGL(k_quality<false>, dim3(tx, ty, n_images), dim3(256), 3 * 256 * sizeof(unsigned long long), s, a, b, P,
+                           sse_part, ssim_part);
+    }
+    const double n_windows = ssim_out ? (double)(P.W - 10) * (double)(P.H - 10) : 1.0;
+    hipLaunchKernelGGL(k_quality_sum, dim3(3 * n_images), dim3(256), 256 * (sizeof(unsigned long long) + sizeof(double)), s, sse_part, ssim_part,
+                       (int)(tx * ty), n_windows, sse_out, ssim_out);
+    return hipGetLastError();
+}
+
 }  // namespace tfft
