@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <complex>
+#include <initializer_list>
 #include <map>
 #include <tuple>
 #include <new>
@@ -235,6 +236,27 @@ enum Stage { ROWS_FWD = 0, COLS_FWD_A = 1, COLS_FWD_B = 2, EMBED = 3, COLS_INV_A
 
 int get_dc_table(tfft_ctx* c, int valid, int N, int center, int kind, double scale, const float2** out);
 void invalidate_graphs(tfft_ctx* c);      // cached launch sequences hold raw device pointers: dropped whenever a buffer is reallocated
+
+// Quiesce, then free: before a device buffer goes away that enqueued work or a cached sequence may still name, both compute streams are
+// drained and the cached sequences dropped.  (Every batched call joins stream2 into stream before it returns: the second wait is free.)
+int quiesce(tfft_ctx* c) {
+    const hipError_t e1 = hipStreamSynchronize(c->stream);
+    const hipError_t e2 = c->stream2 ? hipStreamSynchronize(c->stream2) : hipSuccess;
+    invalidate_graphs(c);
+    if (e1 != hipSuccess || e2 != hipSuccess) { c->last_hip = (int)(e1 != hipSuccess ? e1 : e2); return TFFT_E_HIP; }
+    return TFFT_OK;
+}
+// the growth policy of the buffers sized by a call's arguments: a quarter of headroom, so that slowly growing requests do not reallocate each time
+inline uint64_t grown(uint64_t n, uint64_t pad) { return n + n / 4 + pad; }
+// the buffers of one group replaced (the owner records capacity 0 before and the new one after: a group that failed grows again next time)
+struct Regrow { void** p; size_t bytes; };
+int regrow(tfft_ctx* c, std::initializer_list<Regrow> bufs) {
+    int rc = quiesce(c);
+    if (rc) return rc;
+    for (const Regrow& b : bufs) { (void)hipFree(*b.p); *b.p = nullptr; }
+    for (const Regrow& b : bufs) if (dev_alloc(c, b.p, b.bytes)) return TFFT_E_NOMEM;
+    return TFFT_OK;
+}
 
 static void copy_embed_fields(ColParams& cp, const ColParams& e, bool inverse) {
     cp.rd_bins = e.rd_bins; cp.rd_off = e.rd_off; cp.trash = e.trash; cp.rd_walks = e.rd_walks;
@@ -486,14 +508,10 @@ static bool stats_m2_applies(const tfft_ctx* c, const Slot& s, const CapParams& 
 
 int ensure_stage(tfft_ctx* c, uint64_t n) {
     if (n <= c->stage_cap) return TFFT_OK;
-    (void)hipStreamSynchronize(c->stream);
-    invalidate_graphs(c);
-    if (c->stage_bins) { (void)hipFree(c->stage_bins); (void)hipFree(c->stage_bits); (void)hipFree(c->stage_jit); (void)hipFree(c->stage_out); }
-    c->stage_bins = c->stage_bits = c->stage_jit = c->stage_out = nullptr; c->stage_cap = 0;
-    size_t cap = (size_t)n + (size_t)n / 4 + 1024;
-    if (dev_alloc(c, &c->stage_bins, cap * sizeof(tfft_bin)) || dev_alloc(c, &c->stage_bits, cap) ||
-        dev_alloc(c, &c->stage_jit, cap * sizeof(float)) || dev_alloc(c, &c->stage_out, cap))
-        return TFFT_E_NOMEM;
+    c->stage_cap = 0;
+    const size_t cap = grown(n, 1024);
+    int rc = regrow(c, {{&c->stage_bins, cap * sizeof(tfft_bin)}, {&c->stage_bits, cap}, {&c->stage_jit, cap * sizeof(float)}, {&c->stage_out, cap}});
+    if (rc) return rc;
     c->stage_cap = cap;
     return TFFT_OK;
 }
@@ -763,7 +781,51 @@ int exact_buffers(tfft_ctx* c) {
 bool exact_possible(const tfft_ctx* c, const Slot& s) {
     return c->exact_stats && s.rgb_src && s.PW == s.PWi && s.PWi <= 8192 && s.PH <= 65535 && s.PWi <= 65535;
 }
-struct ExactOut { std::vector<ExactCand> cand[3]; std::vector<double> mag[3]; unsigned long long outside[3]; };
+// exp(2 pi i j/PW) in fp64 (device), made once per width
+int exact_table(tfft_ctx* c, int PW, const double2** out) {
+    auto it = c->ex_table.find(PW);
+    if (it != c->ex_table.end()) { *out = it->second; return TFFT_OK; }
+    double2* t = nullptr;
+    if (dev_alloc(c, (void**)&t, (size_t)PW * sizeof(double2))) return TFFT_E_NOMEM;
+    HIPCHK(c, launch_exact_table(t, PW, c->stream));
+    c->ex_table[PW] = t;
+    *out = t;
+    return TFFT_OK;
+}
+// the row bands a candidate's sum is dealt to: the single-image and the batched calls cut alike, hence add the same partials
+int exact_split(int H) { return std::min(std::max(H / 32, 1), EX_SPLIT); }
+// ---- the decision rules of the exact statistics, one copy for the single-image calls and the batched embeds (DESIGN.md section 11 promises
+// that they agree).  A candidate: its fp64 magnitude (std::abs(complex<double>) of S:406 / S:1004), its fp32 |F|^2, the weight it carries
+struct ExactPt { double mag; float m2; unsigned long long w; };
+double exact_emax(const std::vector<ExactPt>& pt) {
+    double emax = 0.0;
+    for (const ExactPt& q : pt) emax = fmax(emax, fabs(q.mag - sqrt((double)q.m2)));
+    return emax;      // the largest fp32 error seen on a window's own bins
+}
+// Median (median_abs, S:404-409) from the candidates of a window of relative half-width rel around the fp32 median m32 and the weight below
+// it.  False (widen) unless the window holds the rank and is 4 x wider than the error seen on its own bins (else a bin outside could belong inside)
+bool exact_median_rule(const std::vector<ExactPt>& pt, unsigned long long outside, unsigned long long rank, double rel, float m32, double* med) {
+    unsigned long long wsum = 0;
+    for (const ExactPt& q : pt) wsum += q.w;
+    if (!(outside <= rank && rank < outside + wsum) || 4.0 * exact_emax(pt) > rel * (double)m32) return false;
+    std::vector<size_t> ord(pt.size());
+    for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
+    std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return pt[a].mag < pt[b].mag; });
+    unsigned long long cum = outside;
+    *med = (double)m32;
+    for (size_t k = 0; k < ord.size(); k++) { cum += pt[ord[k]].w; if (rank < cum) { *med = pt[ord[k]].mag; break; } }
+    return true;
+}
+// Count (S:998-1008) of one plane: the weight outside the window plus the candidates not below thr, halved; false (widen) as above
+bool exact_count_rule(const std::vector<ExactPt>& pt, unsigned long long outside, double rel, double thr, unsigned long long* count) {
+    unsigned long long cnt = outside;
+    for (const ExactPt& q : pt)
+        if (!(q.mag < thr)) cnt += q.w;          // S:1004: `if (std::abs(F) < thr) continue`
+    if (4.0 * exact_emax(pt) > rel * thr) return false;
+    *count = cnt / 2;                            // S:1007: c/2 per plane
+    return true;
+}
+struct ExactOut { std::vector<ExactPt> pt[3]; unsigned long long outside[3]; };
 // one collect + evaluate round with the fp32 |F|^2 windows [lo2, hi2] per plane; false in `ok` when a candidate list overflowed
 int exact_round(tfft_ctx* c, int slot, const ExactCollect& P, ExactOut& o, bool& ok) {
     const Slot& s = c->slots[slot];
@@ -776,34 +838,27 @@ int exact_round(tfft_ctx* c, int slot, const ExactCollect& P, ExactOut& o, bool&
     HIPCHK(c, hipStreamSynchronize(c->stream));
     ok = n[0] <= (unsigned)EX_CAP && n[1] <= (unsigned)EX_CAP && n[2] <= (unsigned)EX_CAP;
     if (!ok) return TFFT_OK;
-    double2* table = nullptr;
-    {
-        auto it = c->ex_table.find(s.PWi);
-        if (it == c->ex_table.end()) {
-            if (dev_alloc(c, (void**)&table, (size_t)s.PWi * sizeof(double2))) return TFFT_E_NOMEM;
-            HIPCHK(c, launch_exact_table(table, s.PWi, c->stream));
-            c->ex_table[s.PWi] = table;
-        } else table = it->second;
-    }
-    int split = s.H / 32;
-    if (split < 1) split = 1;
-    if (split > EX_SPLIT) split = EX_SPLIT;
+    const double2* table = nullptr;
+    rc = exact_table(c, s.PWi, &table);
+    if (rc) return rc;
+    const int split = exact_split(s.H);
     for (int p = 0; p < 3; p++) {
-        o.cand[p].resize(n[p]); o.mag[p].resize(n[p]);
+        o.pt[p].resize(n[p]);
         if (!n[p]) continue;
         HIPCHK(c, launch_exact_eval(s.rgb_src, s.W, s.H, s.PWi, s.PH, s.center, c->ex_cand + (size_t)p * EX_CAP, n[p], split, table,
                                     c->ex_val + (size_t)p * EX_CAP * EX_SPLIT, c->stream));
     }
     std::vector<double2> v((size_t)EX_CAP * EX_SPLIT);
+    std::vector<ExactCand> cand((size_t)EX_CAP);
     for (int p = 0; p < 3; p++) {
         if (!n[p]) continue;
-        HIPCHK(c, hipMemcpyAsync(o.cand[p].data(), c->ex_cand + (size_t)p * EX_CAP, n[p] * sizeof(ExactCand), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(cand.data(), c->ex_cand + (size_t)p * EX_CAP, n[p] * sizeof(ExactCand), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(v.data(), c->ex_val + (size_t)p * EX_CAP * EX_SPLIT, (size_t)n[p] * split * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (unsigned i = 0; i < n[p]; i++) {
             double re = 0.0, im = 0.0;
             for (int k = 0; k < split; k++) { re += v[(size_t)i * split + k].x; im += v[(size_t)i * split + k].y; }      // fixed order: deterministic
-            o.mag[p][i] = hypot(re, im);      // std::abs(complex<double>) of S:406 / S:1004
+            o.pt[p][i] = ExactPt{hypot(re, im), cand[i].m2, cand[i].w};
         }
     }
     return TFFT_OK;
@@ -832,29 +887,64 @@ bool exact_medians(tfft_ctx* c, int slot, const float m32[3], double med[3], int
         if (!ok) return false;           // a flat spectrum (thousands of bins within 1e-6 of the median): keep the fp32 answer
         bool good = true;
         for (int p = 0; p < 3 && good; p++) {
-            const size_t n = o.cand[p].size();
-            unsigned long long wsum = 0; double emax = 0.0;
-            for (size_t i = 0; i < n; i++) { wsum += o.cand[p][i].w; emax = fmax(emax, fabs(o.mag[p][i] - sqrt((double)o.cand[p][i].m2))); }
-            // the window must hold the rank, and be wide against the fp32 error actually seen on its own bins (else a bin outside it
-            // could belong inside): 4 x the largest error
-            if (!(o.outside[p] <= rank && rank < o.outside[p] + wsum) || 4.0 * emax > rel * (double)m32[p]) { good = false; break; }
-            std::vector<size_t> ord(n);
-            for (size_t i = 0; i < n; i++) ord[i] = i;
-            std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return o.mag[p][a] < o.mag[p][b]; });
-            unsigned long long cum = o.outside[p];
-            med[p] = (double)m32[p];
-            for (size_t k = 0; k < n; k++) { cum += o.cand[p][ord[k]].w; if (rank < cum) { med[p] = o.mag[p][ord[k]]; break; } }
-            c->ex_last[p] = (int)n;
+            good = exact_median_rule(o.pt[p], o.outside[p], rank, rel, m32[p], &med[p]);
+            if (good) c->ex_last[p] = (int)o.pt[p].size();
         }
         if (good) return true;
     }
     return false;
 }
+// Stream framing (S:986-995): a header byte becomes 24 stream bits (8 bits, each three times), a payload byte 56 (each seven times)
+constexpr uint64_t kHeaderBytes = 38, kBitsPerHeaderByte = 24, kBitsPerPayloadByte = 56;
+constexpr uint64_t kHeaderBits = kHeaderBytes * kBitsPerHeaderByte;      // 912
+inline uint64_t stream_bits(uint64_t payload_len) { return kHeaderBits + payload_len * kBitsPerPayloadByte; }
+// does the stream of a payload fit a walk of n_bins?  (Divides before it multiplies: a huge length must not wrap)
+inline bool stream_fits(uint64_t n_bins, uint64_t payload_len) {
+    return n_bins >= kHeaderBits && payload_len <= (n_bins - kHeaderBits) / kBitsPerPayloadByte;
+}
+// What a batched call hands each of its chunks: everything but the slots, the stream and the chunk's images and outputs.  The per-image
+// arrays (device) are those of the chunk's first image; from(i) moves them on by i images and is the one place that states their strides.
+struct ChunkArgs {
+    const tfft_bin* bins = nullptr;      // one list of n_bits bins for every image (per_image: one list each)
+    uint64_t n_bits = 0;
+    double alpha = 0.0;
+    double rmin = 0.0, rmax = 0.0, magmin = 0.0;      // the annulus and the threshold of the capacities (embeds)
+    // the bit source of an embed: one byte per bit, n_bits per image -- or the packed frames of the stream pipelines (kHeaderBytes + plen
+    // bytes per image), expanded by the kernels on the way: `limit` stream bits per image, the bin list may be longer
+    const uint8_t* bits = nullptr;
+    const uint8_t* hdr = nullptr; const uint8_t* pay = nullptr; uint64_t plen = 0, limit = ~0ull;
+    // one walk per image (tfft_*_stream_batch_walks*, the fitted embed): `bins` are a chunk's g lists, image i's at bins + i*n_bits; jitter
+    // (the same layout, or nullptr) and adaptive alpha come with them instead of from the context's phase options
+    bool per_image = false; const float* jit = nullptr; bool adaptive = false;
+    static ChunkArgs list(const void* bins, uint64_t n_bits, double alpha) {
+        ChunkArgs a;
+        a.bins = (const tfft_bin*)bins; a.n_bits = n_bits; a.alpha = alpha;
+        return a;
+    }
+    ChunkArgs& capacity(double lo, double hi, double mm) { rmin = lo; rmax = hi; magmin = mm; return *this; }
+    ChunkArgs& plain(const void* b) { bits = (const uint8_t*)b; return *this; }
+    ChunkArgs& frames(const void* h, const void* p, uint64_t len) {
+        hdr = (const uint8_t*)h; pay = (const uint8_t*)p; plen = len; limit = stream_bits(len);      // S:986-995
+        return *this;
+    }
+    ChunkArgs& walks(const void* j, int adapt) { per_image = true; jit = (const float*)j; adaptive = adapt != 0; return *this; }
+    bool framed() const { return hdr != nullptr; }
+    uint64_t stream_len() const { return limit < n_bits ? limit : n_bits; }      // the bits an image carries
+    ChunkArgs from(size_t i) const {
+        ChunkArgs a = *this;
+        if (bits) a.bits += i * n_bits;
+        if (hdr) a.hdr += i * kHeaderBytes;
+        if (pay) a.pay += i * plen;
+        if (per_image) { a.bins += i * n_bits; if (jit) a.jit += i * n_bits; }
+        return a;
+    }
+};
 
 // ---- exact capacities of the batched embeds (tfft_set_batch_exact).  A chunk's selected covers get a storing fp32
 // forward into the slot spectra; then the single-image method (exact_medians, tfft_capacity) runs for all of them at once: one collect
 // launch (per-image windows), one evaluate launch (k_exact_eval_batch: TFFT_EXACT_K candidates of an image plane per pass over its pixels),
-// one in-order sum, one read per round.  Rounds and windows follow the single-image calls; an image settles, widens or gives up on its own.
+// one in-order sum, one read per round.  The decisions are the single-image calls' own (exact_median_rule, exact_count_rule), the rounds
+// and windows follow them; an image settles, widens or gives up on its own.
 int bx_buffers(tfft_ctx* c) {
     if (c->bx_win) return TFFT_OK;
     const size_t n = (size_t)c->n_slots, nc = 3 * n * EX_CAP;
@@ -864,7 +954,8 @@ int bx_buffers(tfft_ctx* c) {
         return TFFT_E_NOMEM;
     return TFFT_OK;
 }
-// the partials and settled values of n dense candidates (grown on demand: a round rarely holds more than a few thousand)
+// the partials and settled values of n dense candidates (grown on demand: a round rarely holds more than a few thousand, hence half again,
+// not grown()).  Settling runs on the context's stream after the chunk's streams have joined and is never captured: no quiesce()
 int bx_value_buffers(tfft_ctx* c, size_t n, int split) {
     const size_t np = n * (size_t)split;
     if (np > c->bx_part_cap) {
@@ -883,18 +974,8 @@ int bx_value_buffers(tfft_ctx* c, size_t n, int split) {
     }
     return TFFT_OK;
 }
-int exact_table(tfft_ctx* c, int PW, const double2** out) {
-    auto it = c->ex_table.find(PW);
-    if (it != c->ex_table.end()) { *out = it->second; return TFFT_OK; }
-    double2* t = nullptr;
-    if (dev_alloc(c, (void**)&t, (size_t)PW * sizeof(double2))) return TFFT_E_NOMEM;
-    HIPCHK(c, launch_exact_table(t, PW, c->stream));
-    c->ex_table[PW] = t;
-    *out = t;
-    return TFFT_OK;
-}
 // per (entry, plane) of a round: the candidates' settled values, the weight outside the window, whether the list fit
-struct BxList { std::vector<ExactVal> v; unsigned long long outside = 0; bool ok = false; };
+struct BxList { std::vector<ExactPt> v; unsigned long long outside = 0; bool ok = false; };
 // one collect + evaluate round over the launch entries `win` (spectra at c->spec(s0) + img, covers at cov + img * img_bytes) -> out[3z + p]
 int bx_round(tfft_ctx* c, int s0, const uint8_t* cov, size_t img_bytes, const ExactCollect& P, const std::vector<ExactWin>& win,
              std::vector<BxList>& out, unsigned* max_cand, hipStream_t st) {
@@ -929,9 +1010,7 @@ int bx_round(tfft_ctx* c, int s0, const uint8_t* cov, size_t img_bytes, const Ex
     const double2* table = nullptr;
     int rc = exact_table(c, s.PWi, &table);
     if (rc) return rc;
-    int split = s.H / 32;                // as exact_round: the same row bands, hence the same partials
-    if (split < 1) split = 1;
-    if (split > EX_SPLIT) split = EX_SPLIT;
+    const int split = exact_split(s.H);
     rc = bx_value_buffers(c, idx.size(), split);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->bx_idx, idx.data(), idx.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
@@ -942,15 +1021,16 @@ int bx_round(tfft_ctx* c, int s0, const uint8_t* cov, size_t img_bytes, const Ex
     std::vector<ExactVal> v(idx.size());
     HIPCHK(c, hipMemcpyAsync(v.data(), c->bx_val, v.size() * sizeof(ExactVal), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    for (size_t i = 0; i < idx.size(); i++) out[idx[i] / EX_CAP].v.push_back(v[i]);
+    for (size_t i = 0; i < idx.size(); i++) out[idx[i] / EX_CAP].v.push_back(ExactPt{hypot(v[i].re, v[i].im), v[i].m2, v[i].w});
     return TFFT_OK;
 }
 
 // The chunk in slots [s0, s0+g): covers at cov (g images w*h*3 bytes apart, intact), fp32 medians in c->med, fp32 counts in `usable` (device).
 // Settles the images the mode selects (NEAR: |count - L| <= guard) and overwrites their counts; state[i] = 1 / 0 / -1 (tfft_batch_exact_info).
 // Synchronises st.
-int bx_settle(tfft_ctx* c, int s0, int g, const uint8_t* cov, double rmin, double rmax, double magmin, uint64_t L, unsigned long long* usable,
-              int32_t* state, hipStream_t st) {
+int bx_settle(tfft_ctx* c, int s0, int g, const uint8_t* cov, const ChunkArgs& a, unsigned long long* usable, int32_t* state, hipStream_t st) {
+    const uint64_t L = a.stream_len();
+    const double magmin = a.magmin;
     for (int i = 0; i < g; i++) state[i] = 0;
     if (!c->bx_mode || !usable || g <= 0) return TFFT_OK;
     int rc = bx_buffers(c);
@@ -1010,29 +1090,14 @@ int bx_settle(tfft_ctx* c, int s0, int g, const uint8_t* cov, double rmin, doubl
             const int j = todo[z];
             if (!o[3 * z].ok) continue;                 // a flat spectrum: gives up (state -1), as the single-image call keeps its fp32 answer
             bool good = true;
-            for (int p = 0; p < 3 && good; p++) {
-                const BxList& b = o[3 * z + p];
-                const float mp = m32[3 * sel[j] + p];
-                unsigned long long wsum = 0; double emax = 0.0;
-                std::vector<double> mag(b.v.size());
-                for (size_t i = 0; i < b.v.size(); i++) {
-                    mag[i] = hypot(b.v[i].re, b.v[i].im);
-                    wsum += b.v[i].w; emax = fmax(emax, fabs(mag[i] - sqrt((double)b.v[i].m2)));
-                }
-                if (!(b.outside <= rank && rank < b.outside + wsum) || 4.0 * emax > rel * (double)mp) { good = false; break; }
-                std::vector<size_t> ord(mag.size());
-                for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
-                std::sort(ord.begin(), ord.end(), [&](size_t a, size_t bb) { return mag[a] < mag[bb]; });
-                unsigned long long cum = b.outside;
-                med[3 * j + p] = (double)mp;
-                for (size_t k = 0; k < ord.size(); k++) { cum += b.v[ord[k]].w; if (rank < cum) { med[3 * j + p] = mag[ord[k]]; break; } }
-            }
+            for (int p = 0; p < 3 && good; p++)
+                good = exact_median_rule(o[3 * z + p].v, o[3 * z + p].outside, rank, rel, m32[3 * sel[j] + p], &med[3 * j + p]);
             if (good) done.push_back(j); else again.push_back(j);
         }
         todo.swap(again);
     }
     // capacities: thr = magmin * med, window 1e-3 widened x4, at most 4 rounds (tfft_capacity); a plane with thr <= 0 counts every annulus bin
-    const CapParams cp = cap_params(c, s, rmin, rmax);
+    const CapParams cp = cap_params(c, s, a.rmin, a.rmax);
     P.cap = 1; P.s_lo = cp.s_lo; P.s_hi = cp.s_hi;
     std::vector<unsigned long long> exact_u(u);
     todo.clear();
@@ -1062,17 +1127,9 @@ int bx_settle(tfft_ctx* c, int s0, int g, const uint8_t* cov, double rmin, doubl
             bool good = true;
             unsigned long long total = 0;
             for (int p = 0; p < 3 && good; p++) {
-                const BxList& b = o[3 * z + p];
-                const double thr = magmin * med[3 * j + p];
-                unsigned long long cnt = b.outside;
-                double emax = 0.0;
-                for (const ExactVal& v : b.v) {
-                    const double mag = hypot(v.re, v.im);
-                    emax = fmax(emax, fabs(mag - sqrt((double)v.m2)));
-                    if (!(mag < thr)) cnt += v.w;                            // S:1004
-                }
-                if (4.0 * emax > rel * thr) good = false;
-                total += cnt / 2;                                            // S:1007
+                unsigned long long cnt = 0;
+                good = exact_count_rule(o[3 * z + p].v, o[3 * z + p].outside, rel, magmin * med[3 * j + p], &cnt);
+                total += cnt;
             }
             if (good) { exact_u[sel[j]] = total; state[sel[j]] = 1; }
             else again.push_back(j);
@@ -1159,15 +1216,10 @@ int tfft_capacity(tfft_ctx* c, int slot, double rmin, double rmax, const double 
             bool good = true;
             unsigned long long total = 0;
             for (int q = 0; q < 3 && good; q++) {
-                unsigned long long cnt = o.outside[q];
-                double emax = 0.0;
-                for (size_t i = 0; i < o.cand[q].size(); i++) {
-                    emax = fmax(emax, fabs(o.mag[q][i] - sqrt((double)o.cand[q][i].m2)));
-                    if (!(o.mag[q][i] < thr[q])) cnt += o.cand[q][i].w;          // S:1004: `if (std::abs(F) < thr) continue`
-                }
-                if (4.0 * emax > rel * thr[q]) good = false;
-                total += cnt / 2;                                                  // S:1007: c/2 per plane
-                c->ex_last[q] = (int)o.cand[q].size();
+                unsigned long long cnt = 0;
+                good = exact_count_rule(o.pt[q], o.outside[q], rel, thr[q], &cnt);
+                total += cnt;
+                c->ex_last[q] = (int)o.pt[q].size();
             }
             if (good) { *usable = total; return TFFT_OK; }
         }
@@ -1241,9 +1293,8 @@ int tfft_set_phase_options(tfft_ctx* c, const float* jitter, uint64_t n, int ada
     if (!c || (jitter && n == 0)) return TFFT_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     // calls enqueued before may still read the old array: it goes only once they are done
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
-    invalidate_graphs(c);
+    int rc = quiesce(c);
+    if (rc) return rc;
     c->ph_version++;
     c->ph_adaptive = adaptive_alpha ? 1 : 0;
     if (!jitter) {
@@ -1254,7 +1305,7 @@ int tfft_set_phase_options(tfft_ctx* c, const float* jitter, uint64_t n, int ada
     if (c->ph_n != n || !c->ph_jit) {
         (void)hipFree(c->ph_jit);
         c->ph_jit = nullptr; c->ph_n = 0;
-        int rc = dev_alloc(c, (void**)&c->ph_jit, n * sizeof(float));
+        rc = dev_alloc(c, (void**)&c->ph_jit, n * sizeof(float));
         if (rc) return rc;
     }
     HIPCHK(c, hipMemcpy(c->ph_jit, jitter, n * sizeof(float), hipMemcpyHostToDevice));
@@ -1369,36 +1420,41 @@ static int batch_geometry(tfft_ctx* c, int g, int w, int h, int center) {
     return TFFT_OK;
 }
 
+// the buckets of a bin list: one per (plane, row group of the last forward column step, 16-column tile) of an image like `s` in a launch of g
+struct BucketGeom { int G, ntiles, nb; };
+static BucketGeom bucket_geom(const tfft_ctx* c, const Slot& s, int g) {
+    const ColPlan pl = plan_cols(c, s.PH, s.PWi, g);
+    const int G = pl.direct ? 1 : (1 << pl.log_n1), ntiles = (s.PWi / 2 + 15) / 16;
+    return BucketGeom{G, ntiles, 3 * ntiles * G};
+}
+// the head of a bucketed ColParams: the entries and offsets built on compute stream `which`, and where lanes without an entry store
+static ColParams bucketed_params(const tfft_ctx* c, int which) {
+    ColParams cp{};
+    cp.rd_bins = c->tb[which].ent; cp.rd_off = c->tb[which].off; cp.trash = c->trash;
+    return cp;
+}
+
 // device buffers of the tile buckets for `n` bins and `nb` buckets on compute stream `which`
 static int ensure_buckets(tfft_ctx* c, int which, uint64_t n, int nb, bool with_values = false) {
     auto& b = c->tb[which];
     if (n > b.cap || !b.ent) {
-        (void)hipStreamSynchronize(c->stream);
-        if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-        invalidate_graphs(c);
-        b.built_for = nullptr;
-        (void)hipFree(b.ent); b.ent = nullptr; b.cap = 0;
-        const uint64_t cap = n + n / 4 + 1024;
-        if (dev_alloc(c, (void**)&b.ent, cap * sizeof(TileBin))) return TFFT_E_NOMEM;
+        b.built_for = nullptr; b.cap = 0;
+        const uint64_t cap = grown(n, 1024);
+        const int rc = regrow(c, {{(void**)&b.ent, cap * sizeof(TileBin)}});
+        if (rc) return rc;
         b.cap = cap;
     }
-    if (nb + 1 > b.nb_cap || !b.cnt) {
-        (void)hipStreamSynchronize(c->stream);
-        if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-        invalidate_graphs(c);
-        b.built_for = nullptr;
-        (void)hipFree(b.cnt); (void)hipFree(b.off); b.cnt = b.off = nullptr; b.nb_cap = 0;
-        if (dev_alloc(c, (void**)&b.cnt, (size_t)(nb + 1) * sizeof(unsigned)) || dev_alloc(c, (void**)&b.off, (size_t)(nb + 1 + (nb + 1023) / 1024) * sizeof(unsigned)))
-            return TFFT_E_NOMEM;
+    if (nb + 1 > b.nb_cap || !b.cnt) {      // (sized exactly: the bucket count follows from the geometry, not from the list)
+        b.built_for = nullptr; b.nb_cap = 0;
+        const int rc = regrow(c, {{(void**)&b.cnt, (size_t)(nb + 1) * sizeof(unsigned)}, {(void**)&b.off, (size_t)(nb + 1 + (nb + 1023) / 1024) * sizeof(unsigned)}});
+        if (rc) return rc;
         b.nb_cap = nb + 1;
     }
     if (with_values && (n * (uint64_t)c->n_slots > b.fl_cap || !b.fl)) {
-        (void)hipStreamSynchronize(c->stream);
-        if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-        invalidate_graphs(c);
-        (void)hipFree(b.fl); (void)hipFree(b.pb); b.fl = nullptr; b.pb = nullptr; b.fl_cap = 0;
-        const uint64_t cap = (n + n / 4 + 1024) * (uint64_t)c->n_slots;
-        if (dev_alloc(c, (void**)&b.fl, cap * sizeof(float2)) || dev_alloc(c, (void**)&b.pb, cap)) return TFFT_E_NOMEM;
+        b.fl_cap = 0;
+        const uint64_t cap = grown(n, 1024) * (uint64_t)c->n_slots;
+        const int rc = regrow(c, {{(void**)&b.fl, cap * sizeof(float2)}, {(void**)&b.pb, cap}});
+        if (rc) return rc;
         b.fl_cap = cap;
     }
     return TFFT_OK;
@@ -1429,19 +1485,24 @@ static int build_buckets(tfft_ctx* c, int which, const tfft_bin* bins, uint64_t 
     return TFFT_OK;
 }
 
+// room for n jitter phasors in bucket order on compute stream `which` (whatever was gathered there is gone when it grows)
+static int ensure_jitter(tfft_ctx* c, int which, uint64_t n) {
+    auto& tb = c->tb[which];
+    if (n <= tb.jp_cap && tb.jp) return TFFT_OK;
+    tb.jp_cap = 0; tb.jp_for = 0;
+    const uint64_t cap = grown(n, 1024);
+    int rc = regrow(c, {{(void**)&tb.jp, cap * sizeof(float2)}});
+    if (rc) return rc;
+    tb.jp_cap = cap;
+    return TFFT_OK;
+}
+
 // the phase options' jitter in the order of the buckets just built (once per bucket build and setting: a registered list keeps it)
 static int gather_jitter(tfft_ctx* c, int which, uint64_t n_bits, int nb, hipStream_t st) {
     auto& tb = c->tb[which];
     if (!c->ph_jit) return TFFT_OK;
-    if (n_bits > tb.jp_cap || !tb.jp) {
-        (void)hipStreamSynchronize(c->stream);
-        if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-        invalidate_graphs(c);
-        (void)hipFree(tb.jp); tb.jp = nullptr; tb.jp_cap = 0; tb.jp_for = 0;
-        const uint64_t cap = n_bits + n_bits / 4 + 1024;
-        if (dev_alloc(c, (void**)&tb.jp, cap * sizeof(float2))) return TFFT_E_NOMEM;
-        tb.jp_cap = cap;
-    }
+    int rc = ensure_jitter(c, which, n_bits);
+    if (rc) return rc;
     if (tb.jp_for != c->ph_version) {
         if (tb.jp_for) c->graphs_stale = true;      // (as for the buckets: a captured sequence without this gather must not be replayed)
         HIPCHK(c, launch_gather_jitter(tb.ent, tb.off + nb, c->ph_jit, n_bits, tb.jp, st));
@@ -1459,6 +1520,25 @@ static hipError_t create_stats_stream(tfft_ctx* c, hipStream_t* out) {
     if (c->stats_prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi)
         return hipStreamCreateWithPriority(out, hipStreamNonBlocking, lo);      // numerically greatest = lowest priority
     return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
+}
+
+// the statistics' side stream of compute stream `which` (created on first use) forked off st ...
+static int stats_fork(tfft_ctx* c, int which, hipStream_t st, hipStream_t* side) {
+    if (!c->stream_stats[which]) {
+        HIPCHK(c, create_stats_stream(c, &c->stream_stats[which]));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_stats_fork[which], hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_stats_join[which], hipEventDisableTiming));
+    }
+    HIPCHK(c, hipEventRecord(c->ev_stats_fork[which], st));
+    HIPCHK(c, hipStreamWaitEvent(c->stream_stats[which], c->ev_stats_fork[which], 0));
+    *side = c->stream_stats[which];
+    return TFFT_OK;
+}
+// ... and joined back into it: whoever waits for st has the statistics too
+static int stats_join(tfft_ctx* c, int which, hipStream_t st) {
+    HIPCHK(c, hipEventRecord(c->ev_stats_join[which], c->stream_stats[which]));
+    HIPCHK(c, hipStreamWaitEvent(st, c->ev_stats_join[which], 0));
+    return TFFT_OK;
 }
 
 // Do the statistics of a batched delta embed run inside the last forward column step (COLS_STAT)?  Two-step column plans with 16 .. 512
@@ -1563,68 +1643,38 @@ static int enqueue_forward_tilestats(tfft_ctx* c, int s0, int g, const uint8_t* 
     return TFFT_OK;
 }
 
-struct FrameSrc { const uint8_t* hdr; const uint8_t* pay; uint64_t plen; };      // packed frames of a chunk (device), image i at hdr + 38*i / pay + plen*i
-// one walk per image (tfft_*_stream_batch_walks*): the chunk's `bins` are g lists of n_bits, image i's at bins + i*n_bits; jitter (device, the
-// same layout, or nullptr) and adaptive alpha come with them instead of from the context's phase options
-struct WalkSrc { const float* jit; int adaptive; };
 // the per-image lists of a chunk bucketed (launch_bucket_walks) on compute stream `which`: the shared-list buckets there are gone
-static int build_buckets_walks(tfft_ctx* c, int which, const tfft_bin* bins, uint64_t n_bits, int g, const Slot& s, int G, const float* jit,
-                               hipStream_t st) {
-    const int ntiles = (s.PWi / 2 + 15) / 16, nbt = 3 * ntiles * G * g + 1;      // (+ the invalid bins' bucket)
-    if ((uint64_t)g * n_bits > 0xFFFFFFFFull || (uint64_t)3 * ntiles * G * g + 1 > 1024ull * 1024ull) return TFFT_E_TOO_LARGE;
-    int rc = ensure_buckets(c, which, (uint64_t)g * n_bits, nbt);
+static int build_buckets_walks(tfft_ctx* c, int which, const tfft_bin* bins, uint64_t n_bits, int g, const Slot& s, const BucketGeom& bg,
+                               const float* jit, hipStream_t st) {
+    const int G = bg.G;
+    if ((uint64_t)g * n_bits > 0xFFFFFFFFull || (uint64_t)bg.nb * g + 1 > 1024ull * 1024ull) return TFFT_E_TOO_LARGE;
+    int rc = ensure_buckets(c, which, (uint64_t)g * n_bits, bg.nb * g + 1);      // (+ the invalid bins' bucket)
     if (rc) return rc;
     auto& tb = c->tb[which];
     if (tb.built_for) c->graphs_stale = true;      // a sequence captured for a registered list left its bucket build out
     tb.built_for = nullptr; tb.jp_for = 0; tb.row_for = nullptr;
     HIPCHK(c, launch_bucket_walks(bins, n_bits, g, s.PH, s.PWi, G, tb.cnt, tb.off, tb.ent, c->err, st));
     if (!jit) return TFFT_OK;
-    const uint64_t need = (uint64_t)g * n_bits;
-    if (need > tb.jp_cap || !tb.jp) {
-        (void)hipStreamSynchronize(c->stream);
-        if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-        invalidate_graphs(c);
-        (void)hipFree(tb.jp); tb.jp = nullptr; tb.jp_cap = 0;
-        const uint64_t cap = need + need / 4 + 1024;
-        if (dev_alloc(c, (void**)&tb.jp, cap * sizeof(float2))) return TFFT_E_NOMEM;
-        tb.jp_cap = cap;
-    }
+    rc = ensure_jitter(c, which, (uint64_t)g * n_bits);
+    if (rc) return rc;
     HIPCHK(c, launch_gather_jitter_walks(tb.ent, jit, n_bits, g, tb.jp, st));
     return TFFT_OK;
 }
-static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, const tfft_bin* bins, const uint8_t* bits,
-                            uint64_t n_bits, double alpha, double rmin, double rmax, double magmin,
-                            unsigned long long* usable, uint8_t* rgb_out, hipStream_t st, uint64_t limit, const FrameSrc* frame, const WalkSrc* walks);
-static int embed_chunk(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, const tfft_bin* bins, const uint8_t* bits,
-                       uint64_t n_bits, double alpha, double rmin, double rmax, double magmin,
-                       unsigned long long* usable, uint8_t* rgb_out, hipStream_t st, uint64_t limit = ~0ull, const FrameSrc* frame = nullptr,
-                       const WalkSrc* walks = nullptr) {
-    // adaptive alpha needs every image's medians before the embed: the statistics run whether or not the caller asked for the
-    // capacities (these then land in the context's own buffer)
-    if (!usable && (walks ? walks->adaptive : c->ph_adaptive) && n_bits > 0) usable = c->usable + s0;
-    int rc = usable ? stats_clean_if_dirty(c, st) : TFFT_OK;
-    if (!rc) rc = embed_chunk_impl(c, s0, g, rgb_in, bins, bits, n_bits, alpha, rmin, rmax, magmin, usable, rgb_out, st, limit, frame, walks);
-    if (!rc && usable && c->stats_fail_once) {      // test hook (TFFT_STATS_FAIL_ONCE): as if the sequence had broken off -- garbage in the select state, an error out
-        c->stats_fail_once = 0;
-        HIPCHK(c, hipMemsetAsync(c->sel, 0x01, (size_t)c->n_slots * 3 * sizeof(SelectState), st));
-        rc = TFFT_E_HIP;
-    }
-    if (rc && usable) c->stats_dirty = true;      // (the statistics may have been cut off between two of their launches)
-    return rc;
-}
-static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, const tfft_bin* bins, const uint8_t* bits,
-                            uint64_t n_bits, double alpha, double rmin, double rmax, double magmin,
-                            unsigned long long* usable, uint8_t* rgb_out, hipStream_t st, uint64_t limit, const FrameSrc* frame, const WalkSrc* walks) {
+static int embed_chunk_impl(tfft_ctx* c, int s0, int g, hipStream_t st, const ChunkArgs& a, const uint8_t* rgb_in, unsigned long long* usable,
+                            uint8_t* rgb_out) {
     const Slot& s = c->slots[s0];
+    const uint64_t n_bits = a.n_bits;
+    const double alpha = a.alpha;
+    const bool walks = a.per_image;
     if (!index_ok(c, n_bits) || !phase_ok(c, n_bits)) return TFFT_E_STATE;
     if (walks && (c->bit_index || c->ph_jit)) return TFFT_E_STATE;      // (the shared-list state does not mix with per-image walks)
-    const bool adaptive = walks ? walks->adaptive != 0 : c->ph_adaptive != 0;
-    const float* jit = walks ? walks->jit : c->ph_jit;
+    const bool adaptive = walks ? a.adaptive : c->ph_adaptive != 0;
+    const float* jit = walks ? a.jit : c->ph_jit;
     EmbedParams ep = embed_params(c, s, n_bits, alpha, adaptive, nullptr, jit != nullptr);
     if (walks) ep.bins_stride = n_bits;
     if (adaptive) ep.med_dev = c->med + 3 * s0;      // (the statistics below run before the embed: see `async`)
-    if (limit < n_bits) ep.limit = limit;      // the stream is shorter than the bin list (image i's bits still n_bits apart)
-    if (frame) { ep.frame_hdr = frame->hdr; ep.frame_pay = frame->pay; ep.frame_plen = frame->plen; }
+    if (a.limit < n_bits) ep.limit = a.limit;      // the stream is shorter than the bin list (image i's bits still n_bits apart)
+    if (a.framed()) { ep.frame_hdr = a.hdr; ep.frame_pay = a.pay; ep.frame_plen = a.plen; }
     // Delta embedding.  The inverse transform is linear and IFFT(F) is the cover itself, so the stego image is cover + IFFT(F' - F),
     // and F' - F is zero but for the bins of the list.  The bins are bucketed by column tile (the buckets extraction uses); the last
     // forward column step, which has every tile in LDS, writes the values of the listed bins out in bucket order; the first inverse
@@ -1636,51 +1686,44 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
     ColParams em{};
     int rc;
     if (delta) {
-        const ColPlan pl = plan_cols(c, s.PH, s.PWi, g);
-        const int G = pl.direct ? 1 : (1 << pl.log_n1), ntiles = (s.PWi / 2 + 15) / 16, nb = 3 * ntiles * G;
+        const BucketGeom bg = bucket_geom(c, s, g);
+        const int nb = bg.nb;
         rc = ensure_buckets(c, which, n_bits, nb, true);
         if (rc) return rc;
-        rc = walks ? build_buckets_walks(c, which, bins, n_bits, g, s, G, jit, st) : build_buckets(c, which, bins, n_bits, s, G, st);
+        rc = walks ? build_buckets_walks(c, which, a.bins, n_bits, g, s, bg, jit, st) : build_buckets(c, which, a.bins, n_bits, s, bg.G, st);
         if (rc) return rc;
         auto& tb = c->tb[which];
-        em.rd_bins = tb.ent; em.rd_off = tb.off; em.trash = c->trash; em.em_fl = tb.fl + (size_t)s0 * n_bits; em.em_pb = tb.pb + (size_t)s0 * n_bits;
+        em = bucketed_params(c, which);
+        em.em_fl = tb.fl + (size_t)s0 * n_bits; em.em_pb = tb.pb + (size_t)s0 * n_bits;
         em.em_n = walks ? 0 : n_bits; em.em_cos = ep.cos_a; em.em_sin = ep.sin_a; em.rd_walks = walks ? 1 : 0;      // (walks: entry indices are absolute)
         if (!walks) rc = gather_jitter(c, which, n_bits, nb, st);
         if (rc) return rc;
         em.em_jp = jit ? tb.jp : nullptr;
         em.em_med = adaptive ? c->med + 3 * s0 : nullptr; em.em_alpha = (float)alpha;
         if (usable) {
-            CapParams p0 = cap_params(c, s, rmin, rmax);
+            CapParams p0 = cap_params(c, s, a.rmin, a.rmax);
             if (stats_m2_applies(c, s, p0)) { em.em_m2 = 1; em.st_col0 = c->col0_pool + (size_t)s0 * 3 * s.PH; }
         } else if (c->stats_m2) {      // no capacity asked for: nobody reads the spectrum, the last forward step stores nothing
             em.em_m2 = 2; em.st_col0 = c->col0_pool + (size_t)s0 * 3 * s.PH;
         }
         // the stream bits in bucket order (the packed frames of the stream pipelines are expanded on the way).  (On the side stream
         // beside the forward transform it gained nothing measurable: 0.03 ms of 3.3.)
-        if (walks) HIPCHK(c, launch_gather_bits_walks(tb.ent, bits, ep.frame_hdr, ep.frame_pay, ep.frame_plen, n_bits, ep.limit, g, tb.pb + (size_t)s0 * n_bits, st));
-        else HIPCHK(c, launch_gather_bits(tb.ent, tb.off + nb, bits, ep.frame_hdr, ep.frame_pay, ep.frame_plen, n_bits, ep.limit, g, tb.pb + (size_t)s0 * n_bits, st));
+        if (walks) HIPCHK(c, launch_gather_bits_walks(tb.ent, a.bits, ep.frame_hdr, ep.frame_pay, ep.frame_plen, n_bits, ep.limit, g, tb.pb + (size_t)s0 * n_bits, st));
+        else HIPCHK(c, launch_gather_bits(tb.ent, tb.off + nb, a.bits, ep.frame_hdr, ep.frame_pay, ep.frame_plen, n_bits, ep.limit, g, tb.pb + (size_t)s0 * n_bits, st));
     }
     if (delta && usable) {
         // the statistics' bracket pass inside the last forward column step: neither the spectrum nor |F|^2 is stored (unless a plane's
         // bracket turns out wrong: then the gated plain step produces the spectrum for the fallback kernels)
-        CapParams p = cap_params(c, s, rmin, rmax);
-        p.magmin = magmin;
+        CapParams p = cap_params(c, s, a.rmin, a.rmax);
+        p.magmin = a.magmin;
         if (tilestats_applies(c, s, plan_cols(c, s.PH, s.PWi, g), p, g)) {
             em.em_m2 = 0;
             rc = enqueue_forward_tilestats(c, s0, g, rgb_in, st, em, p, usable, 7);
             if (rc) return rc;
             // the select chain is five small dependent launches: on a side stream beside the inverse transform, which does not wait for it
             hipStream_t sst = st;
-            if (c->stats_async && !adaptive) {
-                if (!c->stream_stats[which]) {
-                    HIPCHK(c, create_stats_stream(c, &c->stream_stats[which]));
-                    HIPCHK(c, hipEventCreateWithFlags(&c->ev_stats_fork[which], hipEventDisableTiming));
-                    HIPCHK(c, hipEventCreateWithFlags(&c->ev_stats_join[which], hipEventDisableTiming));
-                }
-                sst = c->stream_stats[which];
-                HIPCHK(c, hipEventRecord(c->ev_stats_fork[which], st));
-                HIPCHK(c, hipStreamWaitEvent(sst, c->ev_stats_fork[which], 0));
-            }
+            if (c->stats_async && !adaptive) rc = stats_fork(c, which, st, &sst);
+            if (rc) return rc;
             rc = enqueue_tilestats_select(c, s0, g, sst);
             if (rc) return rc;
             if (adaptive) {         // the embed needs the medians: select, gated re-run and fallbacks all finish before the inverse step
@@ -1692,8 +1735,8 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
             rc = enqueue_inverse(c, s0, g, rgb_out, st, mi);
             if (rc) return rc;
             if (sst != st) {
-                HIPCHK(c, hipEventRecord(c->ev_stats_join[which], sst));
-                HIPCHK(c, hipStreamWaitEvent(st, c->ev_stats_join[which], 0));
+                rc = stats_join(c, which, st);
+                if (rc) return rc;
             }
             return adaptive ? TFFT_OK : enqueue_tilestats_tail(c, s0, g, rgb_in, st, p, usable);
         }
@@ -1704,19 +1747,11 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
     if (rc) return rc;
     hipStream_t sst = st;       // the stream the statistics run on
     const bool async = delta && usable && c->stats_async && !adaptive;      // (adaptive: the embed waits for the medians)
-    if (async) {
-        if (!c->stream_stats[which]) {
-            HIPCHK(c, create_stats_stream(c, &c->stream_stats[which]));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_stats_fork[which], hipEventDisableTiming));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_stats_join[which], hipEventDisableTiming));
-        }
-        sst = c->stream_stats[which];
-        HIPCHK(c, hipEventRecord(c->ev_stats_fork[which], st));
-        HIPCHK(c, hipStreamWaitEvent(sst, c->ev_stats_fork[which], 0));
-    }
+    if (async) rc = stats_fork(c, which, st, &sst);
+    if (rc) return rc;
     if (usable) {      // S:922-923, S:998-1012 on the device, no host round trip: capacity is counted inside the median's full pass
-        CapParams p = cap_params(c, s, rmin, rmax);
-        p.magmin = magmin;
+        CapParams p = cap_params(c, s, a.rmin, a.rmax);
+        p.magmin = a.magmin;
         if (c->stats_fused && p.bw > 0) {
             rc = enqueue_medians(c, s0, g, sst, &p, usable, em.em_m2 != 0);
             if (rc) return rc;
@@ -1731,21 +1766,41 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, c
         mi.inv_embed = &em; mi.inv_cover = rgb_in;
         rc = enqueue_inverse(c, s0, g, rgb_out, st, mi);
         if (async) {            // whoever waits for the context's stream has the capacities too
-            HIPCHK(c, hipEventRecord(c->ev_stats_join[which], sst));
-            HIPCHK(c, hipStreamWaitEvent(st, c->ev_stats_join[which], 0));
+            const int rj = stats_join(c, which, st);
+            if (rj) return rj;
         }
         return rc;
     }
-    HIPCHK(c, launch_embed(c->spec(s0), bins, bits, jit, ep, g, c->err, st));
+    HIPCHK(c, launch_embed(c->spec(s0), a.bins, a.bits, jit, ep, g, c->err, st));
     return enqueue_inverse(c, s0, g, rgb_out, st);
 }
-static int extract_chunk(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, const tfft_bin* bins, uint64_t n_bits,
-                         double alpha, uint8_t* bits_out, hipStream_t st, const WalkSrc* walks = nullptr) {
+// one chunk of an embed: the images rgb_in (g of them, packed) through slots [s0, s0+g) on stream st -> rgb_out, capacities -> usable (or nullptr)
+static int embed_chunk(tfft_ctx* c, int s0, int g, hipStream_t st, const ChunkArgs& a, const uint8_t* rgb_in, unsigned long long* usable,
+                       uint8_t* rgb_out) {
+    // adaptive alpha needs every image's medians before the embed: the statistics run whether or not the caller asked for the
+    // capacities (these then land in the context's own buffer)
+    if (!usable && (a.per_image ? a.adaptive : c->ph_adaptive != 0) && a.n_bits > 0) usable = c->usable + s0;
+    int rc = usable ? stats_clean_if_dirty(c, st) : TFFT_OK;
+    if (!rc) rc = embed_chunk_impl(c, s0, g, st, a, rgb_in, usable, rgb_out);
+    if (!rc && usable && c->stats_fail_once) {      // test hook (TFFT_STATS_FAIL_ONCE): as if the sequence had broken off -- garbage in the select state, an error out
+        c->stats_fail_once = 0;
+        HIPCHK(c, hipMemsetAsync(c->sel, 0x01, (size_t)c->n_slots * 3 * sizeof(SelectState), st));
+        rc = TFFT_E_HIP;
+    }
+    if (rc && usable) c->stats_dirty = true;      // (the statistics may have been cut off between two of their launches)
+    return rc;
+}
+// one chunk of an extract: the images rgb_in (g of them, packed) through slots [s0, s0+g) on stream st -> bits_out, n_bits per image
+static int extract_chunk(tfft_ctx* c, int s0, int g, hipStream_t st, const ChunkArgs& a, const uint8_t* rgb_in, uint8_t* bits_out) {
     const Slot& s = c->slots[s0];
+    const tfft_bin* bins = a.bins;
+    const uint64_t n_bits = a.n_bits;
+    const double alpha = a.alpha;
+    const bool walks = a.per_image;
     if (!index_ok(c, n_bits) || !phase_ok(c, n_bits)) return TFFT_E_STATE;
     if (walks && (c->bit_index || c->ph_jit)) return TFFT_E_STATE;
-    const bool adaptive = walks ? walks->adaptive != 0 : c->ph_adaptive != 0;
-    const float* jit = walks ? walks->jit : c->ph_jit;
+    const bool adaptive = walks ? a.adaptive : c->ph_adaptive != 0;
+    const float* jit = walks ? a.jit : c->ph_jit;
     // adaptive alpha with |alpha| < pi/2: a = alpha*clamp(.., 0.5, 2) keeps the sign of alpha and |a| < pi, so the targets j +- a are
     // symmetric about j and j + pi and the bit is the side of that line -- what the fixed-alpha read decides.
     // Beyond, the decision depends on the medians: the single-image calls cover that case
@@ -1762,18 +1817,18 @@ static int extract_chunk(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, cons
     if (c->tile_read && n_bits > 0 && alpha > 0.0 && alpha < M_PI && (g >= 8 || c->tile_read >= 2 || reg_large)) {
         // The spectrum is only ever read at the bins of the list: bucket them by column tile and let the final
         // forward column step read the bits out of its LDS-resident tiles -- no spectrum store, no k_read.
-        const ColPlan pl = plan_cols(c, s.PH, s.PWi, g);
-        const int G = pl.direct ? 1 : (1 << pl.log_n1), ntiles = (s.PWi / 2 + 15) / 16, nb = 3 * ntiles * G;
+        const BucketGeom bg = bucket_geom(c, s, g);
+        const int nb = bg.nb;
         rc = walks ? TFFT_OK : ensure_buckets(c, which, n_bits, nb);
         if (rc) return rc;
         auto& tb = c->tb[which];
         HIPCHK(c, hipMemsetAsync(bits_out, 0, (size_t)g * n_bits, st));          // bins the walk would never produce read as 0 (k_read does the same)
-        rc = walks ? build_buckets_walks(c, which, bins, n_bits, g, s, G, jit, st) : build_buckets(c, which, bins, n_bits, s, G, st);
+        rc = walks ? build_buckets_walks(c, which, bins, n_bits, g, s, bg, jit, st) : build_buckets(c, which, bins, n_bits, s, bg.G, st);
         if (rc) return rc;
         if (!walks) rc = gather_jitter(c, which, n_bits, nb, st);
         if (rc) return rc;
-        ColParams rd{};
-        rd.rd_bins = tb.ent; rd.rd_off = tb.off; rd.rd_bits = bits_out; rd.rd_n = n_bits; rd.trash = c->trash;
+        ColParams rd = bucketed_params(c, which);
+        rd.rd_bits = bits_out; rd.rd_n = n_bits;
         rd.em_jp = jit ? tb.jp : nullptr; rd.rd_walks = walks ? 1 : 0;
         StageMode md;
         md.fwd_read = &rd;
@@ -1821,32 +1876,50 @@ static int split_join(tfft_ctx* c) {
     return TFFT_OK;
 }
 
-static int embed_batch_dev_impl(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, const void* bins_dev,
-                                const void* bits_dev, uint64_t n_bits, double alpha, double rmin, double rmax, double magmin,
-                                void* usable_out_dev, void* rgb_out_dev, int32_t* bx = nullptr) {
-    const size_t img_bytes = (size_t)w * h * 3;
+}  // extern "C"
+namespace {
+// The slots and the stream of one chunk body: g images, the first of them image i1 of the call, in slots [s0, s0+g) on stream st
+struct Chunk { int i1, s0, g; hipStream_t st; };
+// The device arrays of an embed call.  With bx, the call's state array (bx_begin), the driver keeps the covers (rgb, which rgb_out may
+// overlap) before a chunk and settles its capacities (usable) after it (tfft_set_batch_exact); nullptr for a call that does not settle
+struct EmbedDev { const ChunkArgs& a; const uint8_t* rgb; uint8_t* rgb_out; unsigned long long* usable; int32_t* bx; };
+// image i's entry of a per-image array (nullptr stays nullptr); strides: images w*h*3, headers kHeaderBytes, payloads their length, raw bits n_bins
+template <class T> inline T* nth(T* base, size_t i, size_t stride = 1) { return base ? base + i * stride : nullptr; }
+inline size_t image_bytes(int w, int h) { return (size_t)w * h * 3; }
+// The chunk driver of the device-buffer batch calls: n_slots images at a time get their geometry, then body(Chunk) enqueues them.  split:
+// under TFFT_STREAMS=2 a chunk of >= 8 images goes to the body as two halves on two streams.  The plain and the walks calls split; the shared-
+// list stream pair must not: its extract indexes c->stream_bits and c->stream_plen without a slot offset (the halves would share the bits)
+template <class Body>
+int for_chunks(tfft_ctx* c, int n_images, int w, int h, int center, bool split, const EmbedDev* settle, Body&& body) {
+    const size_t img_bytes = image_bytes(w, h);
+    const bool settles = settle && settle->bx;
     for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
         const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
         int rc = batch_geometry(c, g, w, h, center);
         if (rc) return rc;
-        const uint8_t* cov = (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes;
-        if (bx && c->bx_mode) { cov = bx_keep_covers(c, g, cov, (const uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes, img_bytes, c->stream, &rc); if (rc) return rc; }
+        const uint8_t* cov = settles ? nth(settle->rgb, i0, img_bytes) : nullptr;
+        if (settles && c->bx_mode) { cov = bx_keep_covers(c, g, cov, nth(settle->rgb_out, i0, img_bytes), img_bytes, c->stream, &rc); if (rc) return rc; }
         int h1 = 0;
-        rc = split_fork(c, g, &h1);
-        if (rc) return rc;
+        if (split) { rc = split_fork(c, g, &h1); if (rc) return rc; }
         for (int part = 0; part < (h1 ? 2 : 1); part++) {
-            const int s0 = part ? h1 : 0, gp = h1 ? (part ? g - h1 : h1) : g, i1 = i0 + s0;
-            rc = embed_chunk(c, s0, gp, (const uint8_t*)rgb_dev + (size_t)i1 * img_bytes, (const tfft_bin*)bins_dev,
-                             (const uint8_t*)bits_dev + (size_t)i1 * n_bits, n_bits, alpha, rmin, rmax, magmin,
-                             usable_out_dev ? (unsigned long long*)usable_out_dev + i1 : nullptr,
-                             (uint8_t*)rgb_out_dev + (size_t)i1 * img_bytes, part ? c->stream2 : c->stream);
+            const int s0 = part ? h1 : 0, gp = h1 ? (part ? g - h1 : h1) : g;
+            rc = body(Chunk{i0 + s0, s0, gp, part ? c->stream2 : c->stream});
             if (rc) return rc;
         }
         if (h1) { rc = split_join(c); if (rc) return rc; }
-        if (bx) { rc = bx_settle(c, 0, g, cov, rmin, rmax, magmin, n_bits, (unsigned long long*)usable_out_dev + i0, bx + i0, c->stream); if (rc) return rc; }
+        if (settles) { rc = bx_settle(c, 0, g, cov, settle->a, settle->usable + i0, settle->bx + i0, c->stream); if (rc) return rc; }
     }
     return TFFT_OK;
 }
+// the three device-buffer embeds: every chunk through embed_chunk
+int embed_chunks(tfft_ctx* c, int n_images, int w, int h, int center, bool split, const EmbedDev& e) {
+    const size_t img_bytes = image_bytes(w, h);
+    return for_chunks(c, n_images, w, h, center, split, &e, [&](const Chunk& k) {
+        return embed_chunk(c, k.s0, k.g, k.st, e.a.from(k.i1), nth(e.rgb, k.i1, img_bytes), nth(e.usable, k.i1), nth(e.rgb_out, k.i1, img_bytes));
+    });
+}
+}  // namespace
+extern "C" {
 
 // host-side state a batch call leaves behind (what a graph replay has to redo): geometry set, no spectrum in any slot
 static int batch_after(tfft_ctx* c, int n_images, int w, int h, int center) {
@@ -1862,37 +1935,16 @@ int tfft_embed_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, 
                          void* usable_out_dev, void* rgb_out_dev) {
     if (!c || n_images < 0 || !rgb_dev || !rgb_out_dev || (n_bits && (!bins_dev || !bits_dev))) return TFFT_E_INVALID;
     if (!index_ok(c, n_bits) || !phase_ok(c, n_bits)) return TFFT_E_STATE;
-    int32_t* bx = bx_begin(c, n_images, usable_out_dev);
-    if (bx && c->bx_mode)      // (settling synchronises: never captured or replayed)
-        return embed_batch_dev_impl(c, n_images, rgb_dev, w, h, center, bins_dev, bits_dev, n_bits, alpha, rmin, rmax, magmin, usable_out_dev, rgb_out_dev, bx);
+    const ChunkArgs a = ChunkArgs::list(bins_dev, n_bits, alpha).capacity(rmin, rmax, magmin).plain(bits_dev);
+    EmbedDev e{a, (const uint8_t*)rgb_dev, (uint8_t*)rgb_out_dev, (unsigned long long*)usable_out_dev, bx_begin(c, n_images, usable_out_dev)};
+    if (e.bx && c->bx_mode) return embed_chunks(c, n_images, w, h, center, true, e);      // (settling synchronises: never captured or replayed)
+    e.bx = nullptr;
     std::vector<uint64_t> key = {1, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), key_bits(bits_dev),
                                        n_bits, key_bits(alpha), key_bits(rmin), key_bits(rmax), key_bits(magmin), key_bits(usable_out_dev),
                                        key_bits(rgb_out_dev), key_bits(c->bit_index), key_bits((double)c->dc_bias)};
     phase_key(c, key);
-    return with_graph(c, n_images, key,
-                      [&] { return embed_batch_dev_impl(c, n_images, rgb_dev, w, h, center, bins_dev, bits_dev, n_bits, alpha, rmin, rmax, magmin, usable_out_dev, rgb_out_dev); },
+    return with_graph(c, n_images, key, [&] { return embed_chunks(c, n_images, w, h, center, true, e); },
                       [&] { return batch_after(c, n_images, w, h, center); });
-}
-
-static int extract_batch_dev_impl(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, const void* bins_dev,
-                                  uint64_t n_bits, double alpha, void* bits_out_dev) {
-    const size_t img_bytes = (size_t)w * h * 3;
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
-        int rc = batch_geometry(c, g, w, h, center);
-        if (rc) return rc;
-        int h1 = 0;
-        rc = split_fork(c, g, &h1);
-        if (rc) return rc;
-        for (int part = 0; part < (h1 ? 2 : 1); part++) {
-            const int s0 = part ? h1 : 0, gp = h1 ? (part ? g - h1 : h1) : g, i1 = i0 + s0;
-            rc = extract_chunk(c, s0, gp, (const uint8_t*)rgb_dev + (size_t)i1 * img_bytes, (const tfft_bin*)bins_dev, n_bits, alpha,
-                               (uint8_t*)bits_out_dev + (size_t)i1 * n_bits, part ? c->stream2 : c->stream);
-            if (rc) return rc;
-        }
-        if (h1) { rc = split_join(c); if (rc) return rc; }
-    }
-    return TFFT_OK;
 }
 
 // the generic read path stages its parameter block with a host -> device copy per call: not captured
@@ -1903,48 +1955,28 @@ int tfft_extract_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w
     if (!c || n_images < 0 || !rgb_dev || (n_bits && (!bins_dev || !bits_out_dev))) return TFFT_E_INVALID;
     if (!index_ok(c, n_bits) || !phase_ok(c, n_bits)) return TFFT_E_STATE;
     if (c->ph_adaptive && !(fabs(alpha) < M_PI / 2)) return TFFT_E_INVALID;      // (see extract_chunk)
+    const uint8_t* rgb = (const uint8_t*)rgb_dev;
+    uint8_t* bits_out = (uint8_t*)bits_out_dev;
+    const size_t img_bytes = image_bytes(w, h);
+    const ChunkArgs a = ChunkArgs::list(bins_dev, n_bits, alpha);
     std::vector<uint64_t> key = {2, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), n_bits,
                                        key_bits(alpha), key_bits(bits_out_dev), key_bits(c->bit_index), key_bits((double)c->dc_bias)};
     phase_key(c, key);
-    return with_graph(c, read_is_simple(alpha) ? n_images : 0, key,
-                      [&] { return extract_batch_dev_impl(c, n_images, rgb_dev, w, h, center, bins_dev, n_bits, alpha, bits_out_dev); },
+    auto body = [&](const Chunk& k) { return extract_chunk(c, k.s0, k.g, k.st, a, nth(rgb, k.i1, img_bytes), nth(bits_out, k.i1, n_bits)); };
+    return with_graph(c, read_is_simple(alpha) ? n_images : 0, key, [&] { return for_chunks(c, n_images, w, h, center, true, nullptr, body); },
                       [&] { return batch_after(c, n_images, w, h, center); });
 }
 
 // ---------------------------------------------------------------- packed-byte streams (SURVEY 8 f-3 wired into the pipelines)
-static int ensure_stream(tfft_ctx* c, uint64_t n_bins) {
-    const size_t need = (size_t)c->n_slots * n_bins;
-    if (need <= c->stream_cap && c->stream_plen) return TFFT_OK;
-    (void)hipStreamSynchronize(c->stream);
-    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-    invalidate_graphs(c);
-    (void)hipFree(c->stream_bits); c->stream_bits = nullptr; c->stream_cap = 0;
-    if (dev_alloc(c, (void**)&c->stream_bits, need + 64)) return TFFT_E_NOMEM;
-    c->stream_cap = need;
+// the scratch of the stream calls: the images' payload lengths and, with raw, the raw bits of n_slots whole lists (sized exactly)
+static int ensure_stream(tfft_ctx* c, uint64_t n_bins, bool raw = true) {
     if (!c->stream_plen && dev_alloc(c, (void**)&c->stream_plen, (size_t)c->n_slots * sizeof(unsigned))) return TFFT_E_NOMEM;
-    return TFFT_OK;
-}
-
-static int embed_stream_batch_dev_impl(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, const void* bins_dev,
-                                       uint64_t n_bins, const void* header_dev, const void* payload_dev, uint64_t payload_len, double alpha,
-                                       double rmin, double rmax, double magmin, void* usable_out_dev, void* rgb_out_dev, int32_t* bx = nullptr) {
-    const uint64_t n_bits = 38ull * 24 + payload_len * 56;           // S:986-995
-    int rc = TFFT_OK;
-    const size_t img_bytes = (size_t)w * h * 3;
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
-        rc = batch_geometry(c, g, w, h, center);
-        if (rc) return rc;
-        const uint8_t* cov = (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes;
-        if (bx && c->bx_mode) { cov = bx_keep_covers(c, g, cov, (const uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes, img_bytes, c->stream, &rc); if (rc) return rc; }
-        // bits_from_bytes + rep3/rep7_encode happen inside k_embed: every bin computes its own stream bit from the packed frame
-        const FrameSrc fr{(const uint8_t*)header_dev + (size_t)i0 * 38, (const uint8_t*)payload_dev + (size_t)i0 * payload_len, payload_len};
-        rc = embed_chunk(c, 0, g, (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, (const tfft_bin*)bins_dev, nullptr, n_bins, alpha, rmin, rmax,
-                         magmin, usable_out_dev ? (unsigned long long*)usable_out_dev + i0 : nullptr, (uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes,
-                         c->stream, n_bits, &fr);
-        if (rc) return rc;
-        if (bx) { rc = bx_settle(c, 0, g, cov, rmin, rmax, magmin, n_bits, (unsigned long long*)usable_out_dev + i0, bx + i0, c->stream); if (rc) return rc; }
-    }
+    const size_t need = raw ? (size_t)c->n_slots * n_bins : 0;
+    if (need <= c->stream_cap) return TFFT_OK;
+    c->stream_cap = 0;
+    int rc = regrow(c, {{(void**)&c->stream_bits, need + 64}});
+    if (rc) return rc;
+    c->stream_cap = need;
     return TFFT_OK;
 }
 
@@ -1952,43 +1984,30 @@ int tfft_embed_stream_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, 
                                 uint64_t n_bins, const void* header_dev, const void* payload_dev, uint64_t payload_len, double alpha,
                                 double rmin, double rmax, double magmin, void* usable_out_dev, void* rgb_out_dev) {
     if (!c || n_images < 0 || !rgb_dev || !rgb_out_dev || !bins_dev || !header_dev || (payload_len && !payload_dev)) return TFFT_E_INVALID;
-    if (n_bins < 912 || payload_len > (n_bins - 912) / 56) return TFFT_E_INVALID;      // (before the multiplication: a huge length must not wrap)
-    const uint64_t n_bits = 38ull * 24 + payload_len * 56;           // S:986-995
-    if (n_bits > n_bins) return TFFT_E_INVALID;                      // the caller's walk is shorter than the stream
+    if (!stream_fits(n_bins, payload_len)) return TFFT_E_INVALID;
+    if (stream_bits(payload_len) > n_bins) return TFFT_E_INVALID;      // the caller's walk is shorter than the stream
     if (!index_ok(c, n_bins) || !phase_ok(c, n_bins)) return TFFT_E_STATE;
     int rc = ensure_stream(c, n_bins);                                // (may reallocate: before any cached sequence is looked up)
     if (rc) return rc;
-    int32_t* bx = bx_begin(c, n_images, usable_out_dev);
-    if (bx && c->bx_mode)      // (settling synchronises: never captured or replayed)
-        return embed_stream_batch_dev_impl(c, n_images, rgb_dev, w, h, center, bins_dev, n_bins, header_dev, payload_dev, payload_len, alpha,
-                                           rmin, rmax, magmin, usable_out_dev, rgb_out_dev, bx);
+    // bits_from_bytes + rep3/rep7_encode happen inside k_embed: every bin computes its own stream bit from the packed frame
+    const ChunkArgs a = ChunkArgs::list(bins_dev, n_bins, alpha).capacity(rmin, rmax, magmin).frames(header_dev, payload_dev, payload_len);
+    EmbedDev e{a, (const uint8_t*)rgb_dev, (uint8_t*)rgb_out_dev, (unsigned long long*)usable_out_dev, bx_begin(c, n_images, usable_out_dev)};
+    if (e.bx && c->bx_mode) return embed_chunks(c, n_images, w, h, center, false, e);      // (settling synchronises: never captured or replayed)
+    e.bx = nullptr;
     std::vector<uint64_t> key = {3, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), n_bins,
                                        key_bits(header_dev), key_bits(payload_dev), payload_len, key_bits(alpha), key_bits(rmin), key_bits(rmax),
                                        key_bits(magmin), key_bits(usable_out_dev), key_bits(rgb_out_dev), key_bits(c->bit_index), key_bits((double)c->dc_bias)};
     phase_key(c, key);
-    return with_graph(c, n_images, key,
-                      [&] { return embed_stream_batch_dev_impl(c, n_images, rgb_dev, w, h, center, bins_dev, n_bins, header_dev, payload_dev, payload_len, alpha,
-                                                               rmin, rmax, magmin, usable_out_dev, rgb_out_dev); },
+    return with_graph(c, n_images, key, [&] { return embed_chunks(c, n_images, w, h, center, false, e); },
                       [&] { return batch_after(c, n_images, w, h, center); });
 }
 
-static int extract_stream_batch_dev_impl(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, const void* bins_dev,
-                                         uint64_t n_bins, double alpha, void* header_out_dev, void* payload_out_dev, uint64_t max_payload_len,
-                                         void* status_out_dev, void* raw_bits_out_dev) {
-    int rc = TFFT_OK;
-    const size_t img_bytes = (size_t)w * h * 3;
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
-        rc = batch_geometry(c, g, w, h, center);
-        if (rc) return rc;
-        // every position of the caller's walk is read in the one pass that has the spectrum on chip; the header decides
-        // afterwards how many of them belong to the stream (S:1223-1264: 912 bits, clen, then 56*(clen+16) more)
-        uint8_t* raw = raw_bits_out_dev ? (uint8_t*)raw_bits_out_dev + (size_t)i0 * n_bins : c->stream_bits;
-        rc = extract_chunk(c, 0, g, (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, (const tfft_bin*)bins_dev, n_bins, alpha, raw, c->stream);
-        if (rc) return rc;
-        HIPCHK(c, launch_stream_decode(raw, n_bins, max_payload_len, g, (uint8_t*)header_out_dev + (size_t)i0 * 38,
-                                       (uint8_t*)payload_out_dev + (size_t)i0 * max_payload_len, (int*)status_out_dev + i0, c->stream_plen, c->stream));
-    }
+// The tail of both stream extracts: a chunk's raw bits -> header, payload and status.  Every position of the walk was read in the one pass that
+// had the spectrum on chip; the header decides afterwards how many belong to the stream (S:1223-1264: its own bits, clen, then clen+16 bytes' worth)
+struct DecodeOut { uint8_t* header; uint8_t* payload; uint64_t max_plen; int* status; };
+static int decode_chunk(tfft_ctx* c, const Chunk& k, const uint8_t* raw, uint64_t n_bins, const DecodeOut& o, unsigned* plen) {
+    HIPCHK(c, launch_stream_decode(raw, n_bins, o.max_plen, k.g, nth(o.header, k.i1, kHeaderBytes), nth(o.payload, k.i1, o.max_plen), nth(o.status, k.i1),
+                                   plen, k.st));
     return TFFT_OK;
 }
 
@@ -1999,16 +2018,23 @@ int tfft_extract_stream_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev
         return TFFT_E_INVALID;
     if (!index_ok(c, n_bins) || !phase_ok(c, n_bins)) return TFFT_E_STATE;
     if (c->ph_adaptive && !(fabs(alpha) < M_PI / 2)) return TFFT_E_INVALID;      // (see extract_chunk)
-    int rc = TFFT_OK;
-    if (!raw_bits_out_dev) { rc = ensure_stream(c, n_bins); if (rc) return rc; }
-    else if (!c->stream_plen && dev_alloc(c, (void**)&c->stream_plen, (size_t)c->n_slots * sizeof(unsigned))) return TFFT_E_NOMEM;
+    int rc = ensure_stream(c, n_bins, !raw_bits_out_dev);
+    if (rc) return rc;
+    const uint8_t* rgb = (const uint8_t*)rgb_dev;
+    uint8_t* raw_out = (uint8_t*)raw_bits_out_dev;
+    const size_t img_bytes = image_bytes(w, h);
+    const DecodeOut out{(uint8_t*)header_out_dev, (uint8_t*)payload_out_dev, max_payload_len, (int*)status_out_dev};
+    const ChunkArgs a = ChunkArgs::list(bins_dev, n_bins, alpha);
     std::vector<uint64_t> key = {4, (uint64_t)n_images, key_bits(rgb_dev), (uint64_t)w, (uint64_t)h, (uint64_t)center, key_bits(bins_dev), n_bins,
                                        key_bits(alpha), key_bits(header_out_dev), key_bits(payload_out_dev), max_payload_len, key_bits(status_out_dev),
                                        key_bits(raw_bits_out_dev), key_bits(c->bit_index), key_bits((double)c->dc_bias)};
     phase_key(c, key);
-    return with_graph(c, read_is_simple(alpha) ? n_images : 0, key,
-                      [&] { return extract_stream_batch_dev_impl(c, n_images, rgb_dev, w, h, center, bins_dev, n_bins, alpha, header_out_dev, payload_out_dev,
-                                                                 max_payload_len, status_out_dev, raw_bits_out_dev); },
+    auto body = [&](const Chunk& k) {
+        uint8_t* raw = raw_out ? nth(raw_out, k.i1, n_bins) : c->stream_bits;      // (no slot offset: see for_chunks)
+        const int rc1 = extract_chunk(c, k.s0, k.g, k.st, a, nth(rgb, k.i1, img_bytes), raw);
+        return rc1 ? rc1 : decode_chunk(c, k, raw, n_bins, out, c->stream_plen);
+    };
+    return with_graph(c, read_is_simple(alpha) ? n_images : 0, key, [&] { return for_chunks(c, n_images, w, h, center, false, nullptr, body); },
                       [&] { return batch_after(c, n_images, w, h, center); });
 }
 
@@ -2028,38 +2054,40 @@ static int pipe_init(tfft_ctx* c) {
     return dev_alloc(c, (void**)&c->out_pool, (size_t)c->n_slots * c->img_stride_b + 256);
 }
 
-// packed-byte framing around the host pipeline (tfft_*_stream_batch): header/payload bytes cross PCIe instead of one byte per bit
-struct StreamIO {
-    const uint8_t* header_in = nullptr; const uint8_t* payload_in = nullptr; uint64_t plen = 0;      // embed
-    uint8_t* header_out = nullptr; uint8_t* payload_out = nullptr; uint64_t max_plen = 0; int32_t* status_out = nullptr;   // extract
+// The host arrays of a host-buffer batch call, image i at i times the array's stride; what a call does not use stays nullptr.
+// framed: packed-byte framing around the pipeline (tfft_*_stream_batch*) -- header/payload bytes cross PCIe instead of one byte per bit
+struct HostIO {
+    const uint8_t* rgb = nullptr;
+    const uint8_t* bits = nullptr; uint64_t* usable = nullptr; uint8_t* rgb_out = nullptr;      // embed (usable: optional)
+    uint8_t* bits_out = nullptr;                                                                 // extract (framed: the raw bits, optional)
+    bool framed = false;
+    const uint8_t* header_in = nullptr; const uint8_t* payload_in = nullptr;                     // framed embed, ChunkArgs::plen payload bytes per image
+    uint8_t* header_out = nullptr; uint8_t* payload_out = nullptr; uint64_t max_plen = 0; int32_t* status_out = nullptr;   // framed extract
 };
 static int ensure_stream_io(tfft_ctx* c, uint64_t plen) {
     if (c->sio_hdr && plen <= c->sio_plen) return TFFT_OK;
-    (void)hipStreamSynchronize(c->stream);
-    invalidate_graphs(c);
-    (void)hipFree(c->sio_hdr); (void)hipFree(c->sio_pay); (void)hipFree(c->sio_status);
-    c->sio_hdr = c->sio_pay = nullptr; c->sio_status = nullptr; c->sio_plen = 0;
-    const uint64_t cap = plen + plen / 4 + 64;
-    if (dev_alloc(c, (void**)&c->sio_hdr, (size_t)c->n_slots * 38) || dev_alloc(c, (void**)&c->sio_pay, (size_t)c->n_slots * cap) ||
-        dev_alloc(c, (void**)&c->sio_status, (size_t)c->n_slots * sizeof(int))) return TFFT_E_NOMEM;
+    c->sio_plen = 0;
+    const uint64_t cap = grown(plen, 64);
+    const size_t n = (size_t)c->n_slots;
+    int rc = regrow(c, {{(void**)&c->sio_hdr, n * kHeaderBytes}, {(void**)&c->sio_pay, n * cap}, {(void**)&c->sio_status, n * sizeof(int)}});
+    if (rc) return rc;
     c->sio_plen = cap;
     return TFFT_OK;
 }
 
-// walks != nullptr: `bins` holds one list of n_bits per image (and walks->jit, a host array, its jitter or nullptr); both travel per part
-// of the ring with the images, to the part's share of the staging lists
-static int batch_host(tfft_ctx* c, bool embed, int n_images, const uint8_t* rgb, int w, int h, int center,
-                      const tfft_bin* bins, const uint8_t* bits, uint64_t n_bits, double alpha, double rmin, double rmax,
-                      double magmin, uint64_t* usable, uint8_t* rgb_out, uint8_t* bits_out, const StreamIO* sio = nullptr,
-                      const WalkSrc* walks = nullptr) {
-    int32_t* bx = embed ? bx_begin(c, n_images, usable) : nullptr;
+// call: as for the device forms, but bins (and, per_image, jit) are HOST arrays and the bit source's pointers are unused (io has the host
+// side; the device side is each ring part's share of the staging buffers).  per_image: lists and jitter travel per part with the images
+static int batch_host(tfft_ctx* c, bool embed, int n_images, int w, int h, int center, const ChunkArgs& call, const HostIO& io) {
+    const uint64_t n_bits = call.n_bits;
+    const bool walks = call.per_image;
+    int32_t* bx = embed ? bx_begin(c, n_images, io.usable) : nullptr;
     if (n_images == 0) return TFFT_OK;
     int rc = pipe_init(c);
     if (rc) return rc;
-    if (sio) {
-        rc = ensure_stream_io(c, embed ? sio->plen : sio->max_plen);
+    if (io.framed) {
+        rc = ensure_stream_io(c, embed ? call.plen : io.max_plen);
+        if (!rc) rc = ensure_stream(c, n_bits, false);
         if (rc) return rc;
-        if (!c->stream_plen && dev_alloc(c, (void**)&c->stream_plen, (size_t)c->n_slots * sizeof(unsigned))) return TFFT_E_NOMEM;
     }
     rc = ensure_stage(c, (uint64_t)c->n_slots * n_bits > n_bits ? (uint64_t)c->n_slots * n_bits : n_bits);
     if (rc) return rc;
@@ -2070,7 +2098,7 @@ static int batch_host(tfft_ctx* c, bool embed, int n_images, const uint8_t* rgb,
     // the slots form a ring of up to four parts: copy-in of part k+1..k+3 overlaps the kernels of part k
     const int nhalves = c->n_slots >= 8 ? 4 : (c->n_slots >= 2 ? 2 : 1);
     const int half = c->n_slots / nhalves;
-    if (!walks) HIPCHK(c, hipMemcpyAsync(c->stage_bins, bins, n_bits * sizeof(tfft_bin), hipMemcpyHostToDevice, c->stream));
+    if (!walks) HIPCHK(c, hipMemcpyAsync(c->stage_bins, call.bins, n_bits * sizeof(tfft_bin), hipMemcpyHostToDevice, c->stream));
     int chunk = 0;
     for (int i0 = 0; i0 < n_images; i0 += half, chunk++) {
         const int g = (n_images - i0 < half) ? n_images - i0 : half;
@@ -2080,55 +2108,49 @@ static int batch_host(tfft_ctx* c, bool embed, int n_images, const uint8_t* rgb,
         // copy-in: the half's input buffers are free once the chunk that used them has been computed
         HIPCHK(c, hipStreamWaitEvent(c->s_in, c->ev_comp[hh], 0));
         // the pipeline treats the half's staging area as one packed batch buffer (g images back to back)
-        HIPCHK(c, hipMemcpyAsync(c->img(s0), rgb + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, c->s_in));
+        HIPCHK(c, hipMemcpyAsync(c->img(s0), io.rgb + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, c->s_in));
         tfft_bin* d_bins = (tfft_bin*)c->stage_bins + (walks ? (size_t)s0 * n_bits : 0);
         float* d_jit = (float*)c->stage_jit + (size_t)s0 * n_bits;
         if (walks) {
-            HIPCHK(c, hipMemcpyAsync(d_bins, bins + (size_t)i0 * n_bits, (size_t)g * n_bits * sizeof(tfft_bin), hipMemcpyHostToDevice, c->s_in));
-            if (walks->jit) HIPCHK(c, hipMemcpyAsync(d_jit, walks->jit + (size_t)i0 * n_bits, (size_t)g * n_bits * sizeof(float), hipMemcpyHostToDevice, c->s_in));
+            HIPCHK(c, hipMemcpyAsync(d_bins, call.bins + (size_t)i0 * n_bits, (size_t)g * n_bits * sizeof(tfft_bin), hipMemcpyHostToDevice, c->s_in));
+            if (call.jit) HIPCHK(c, hipMemcpyAsync(d_jit, call.jit + (size_t)i0 * n_bits, (size_t)g * n_bits * sizeof(float), hipMemcpyHostToDevice, c->s_in));
         }
-        const WalkSrc wpart{walks && walks->jit ? d_jit : nullptr, walks ? walks->adaptive : 0};
-        if (embed && !sio) HIPCHK(c, hipMemcpyAsync(d_bits, bits + (size_t)i0 * n_bits, (size_t)g * n_bits, hipMemcpyHostToDevice, c->s_in));
-        if (embed && sio) {      // 38 + plen bytes per image instead of 912 + 56*plen
-            HIPCHK(c, hipMemcpyAsync(c->sio_hdr + (size_t)s0 * 38, sio->header_in + (size_t)i0 * 38, (size_t)g * 38, hipMemcpyHostToDevice, c->s_in));
-            if (sio->plen) HIPCHK(c, hipMemcpyAsync(c->sio_pay + (size_t)s0 * sio->plen, sio->payload_in + (size_t)i0 * sio->plen, (size_t)g * sio->plen, hipMemcpyHostToDevice, c->s_in));
+        if (embed && !io.framed) HIPCHK(c, hipMemcpyAsync(d_bits, io.bits + (size_t)i0 * n_bits, (size_t)g * n_bits, hipMemcpyHostToDevice, c->s_in));
+        if (embed && io.framed) {      // kHeaderBytes + plen bytes per image instead of stream_bits(plen)
+            HIPCHK(c, hipMemcpyAsync(c->sio_hdr + (size_t)s0 * kHeaderBytes, io.header_in + (size_t)i0 * kHeaderBytes, (size_t)g * kHeaderBytes, hipMemcpyHostToDevice, c->s_in));
+            if (call.plen) HIPCHK(c, hipMemcpyAsync(c->sio_pay + (size_t)s0 * call.plen, io.payload_in + (size_t)i0 * call.plen, (size_t)g * call.plen, hipMemcpyHostToDevice, c->s_in));
         }
         HIPCHK(c, hipEventRecord(c->ev_in[hh], c->s_in));
         // compute: needs the inputs, and the half's output buffers drained by the copy-out of two chunks ago
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in[hh], 0));
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_out[hh], 0));
-        uint64_t limit = ~0ull;
-        FrameSrc fr{nullptr, nullptr, 0};
-        if (embed && sio) {      // bits_from_bytes + rep3/rep7 inside k_embed, from the packed frames of this part of the ring
-            limit = 38ull * 24 + sio->plen * 56;
-            fr = FrameSrc{c->sio_hdr + (size_t)s0 * 38, c->sio_pay + (size_t)s0 * sio->plen, sio->plen};
-        }
+        ChunkArgs a = call;      // the part's device arguments
+        a.bins = d_bins; a.jit = walks && call.jit ? d_jit : nullptr;
+        if (embed && io.framed) {      // bits_from_bytes + rep3/rep7 inside k_embed, from the packed frames of this part of the ring
+            a.hdr = c->sio_hdr + (size_t)s0 * kHeaderBytes; a.pay = c->sio_pay + (size_t)s0 * call.plen;
+        } else if (embed) a.bits = d_bits;
         if (embed) {
-            rc = embed_chunk(c, s0, g, c->img(s0), d_bins, sio ? nullptr : d_bits, n_bits, alpha, rmin, rmax, magmin,
-                             usable ? c->usable + s0 : nullptr, c->out_pool + (size_t)s0 * c->img_stride_b, c->stream, limit, sio ? &fr : nullptr,
-                             walks ? &wpart : nullptr);   // packed, like the input
+            rc = embed_chunk(c, s0, g, c->stream, a, c->img(s0), io.usable ? c->usable + s0 : nullptr, c->out_pool + (size_t)s0 * c->img_stride_b);   // packed, like the input
             if (!rc && bx)      // (the part's covers stay in its image buffers until ev_comp)
-                rc = bx_settle(c, s0, g, c->img(s0), rmin, rmax, magmin, sio ? limit : n_bits, c->usable + s0, bx + i0, c->stream);
+                rc = bx_settle(c, s0, g, c->img(s0), a, c->usable + s0, bx + i0, c->stream);
         } else
-            rc = extract_chunk(c, s0, g, c->img(s0), d_bins, n_bits, alpha, d_bout, c->stream, walks ? &wpart : nullptr);
+            rc = extract_chunk(c, s0, g, c->stream, a, c->img(s0), d_bout);
         if (rc) return rc;
-        if (!embed && sio)       // header -> clen -> payload on the device: only packed bytes and a status word go back
-            HIPCHK(c, launch_stream_decode(d_bout, n_bits, sio->max_plen, g, c->sio_hdr + (size_t)s0 * 38, c->sio_pay + (size_t)s0 * sio->max_plen,
+        if (!embed && io.framed)       // header -> clen -> payload on the device: only packed bytes and a status word go back
+            HIPCHK(c, launch_stream_decode(d_bout, n_bits, io.max_plen, g, c->sio_hdr + (size_t)s0 * kHeaderBytes, c->sio_pay + (size_t)s0 * io.max_plen,
                                            c->sio_status + s0, c->stream_plen + s0, c->stream));
         HIPCHK(c, hipEventRecord(c->ev_comp[hh], c->stream));
         // copy-out
         HIPCHK(c, hipStreamWaitEvent(c->s_out, c->ev_comp[hh], 0));
         if (embed) {
-            HIPCHK(c, hipMemcpyAsync(rgb_out + (size_t)i0 * img_bytes, c->out_pool + (size_t)s0 * c->img_stride_b, (size_t)g * img_bytes, hipMemcpyDeviceToHost, c->s_out));
-            if (usable) HIPCHK(c, hipMemcpyAsync(usable + i0, c->usable + s0, (size_t)g * sizeof(uint64_t), hipMemcpyDeviceToHost, c->s_out));
-        } else if (sio) {
-            HIPCHK(c, hipMemcpyAsync(sio->header_out + (size_t)i0 * 38, c->sio_hdr + (size_t)s0 * 38, (size_t)g * 38, hipMemcpyDeviceToHost, c->s_out));
-            if (sio->max_plen) HIPCHK(c, hipMemcpyAsync(sio->payload_out + (size_t)i0 * sio->max_plen, c->sio_pay + (size_t)s0 * sio->max_plen, (size_t)g * sio->max_plen, hipMemcpyDeviceToHost, c->s_out));
-            HIPCHK(c, hipMemcpyAsync(sio->status_out + i0, c->sio_status + s0, (size_t)g * sizeof(int32_t), hipMemcpyDeviceToHost, c->s_out));
-            if (bits_out) HIPCHK(c, hipMemcpyAsync(bits_out + (size_t)i0 * n_bits, d_bout, (size_t)g * n_bits, hipMemcpyDeviceToHost, c->s_out));
-        } else {
-            HIPCHK(c, hipMemcpyAsync(bits_out + (size_t)i0 * n_bits, d_bout, (size_t)g * n_bits, hipMemcpyDeviceToHost, c->s_out));
+            HIPCHK(c, hipMemcpyAsync(io.rgb_out + (size_t)i0 * img_bytes, c->out_pool + (size_t)s0 * c->img_stride_b, (size_t)g * img_bytes, hipMemcpyDeviceToHost, c->s_out));
+            if (io.usable) HIPCHK(c, hipMemcpyAsync(io.usable + i0, c->usable + s0, (size_t)g * sizeof(uint64_t), hipMemcpyDeviceToHost, c->s_out));
+        } else if (io.framed) {
+            HIPCHK(c, hipMemcpyAsync(io.header_out + (size_t)i0 * kHeaderBytes, c->sio_hdr + (size_t)s0 * kHeaderBytes, (size_t)g * kHeaderBytes, hipMemcpyDeviceToHost, c->s_out));
+            if (io.max_plen) HIPCHK(c, hipMemcpyAsync(io.payload_out + (size_t)i0 * io.max_plen, c->sio_pay + (size_t)s0 * io.max_plen, (size_t)g * io.max_plen, hipMemcpyDeviceToHost, c->s_out));
+            HIPCHK(c, hipMemcpyAsync(io.status_out + i0, c->sio_status + s0, (size_t)g * sizeof(int32_t), hipMemcpyDeviceToHost, c->s_out));
         }
+        if (!embed && io.bits_out) HIPCHK(c, hipMemcpyAsync(io.bits_out + (size_t)i0 * n_bits, d_bout, (size_t)g * n_bits, hipMemcpyDeviceToHost, c->s_out));
         HIPCHK(c, hipEventRecord(c->ev_out[hh], c->s_out));
     }
     HIPCHK(c, hipStreamSynchronize(c->s_out));
@@ -2139,27 +2161,35 @@ int tfft_embed_batch(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int h
                      const uint8_t* bits, uint64_t n_bits, double alpha, double rmin, double rmax, double magmin,
                      uint64_t* usable_out, uint8_t* rgb_out) {
     if (!c || n_images < 0 || !rgb || !rgb_out || !bins || !bits || n_bits == 0) return TFFT_E_INVALID;
-    return batch_host(c, true, n_images, rgb, w, h, center, bins, bits, n_bits, alpha, rmin, rmax, magmin, usable_out, rgb_out, nullptr);
+    const ChunkArgs a = ChunkArgs::list(bins, n_bits, alpha).capacity(rmin, rmax, magmin);
+    HostIO io; io.rgb = rgb; io.bits = bits; io.usable = usable_out; io.rgb_out = rgb_out;
+    return batch_host(c, true, n_images, w, h, center, a, io);
 }
 int tfft_extract_batch(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int h, int center, const tfft_bin* bins,
                        uint64_t n_bits, double alpha, uint8_t* bits_out) {
     if (!c || n_images < 0 || !rgb || !bins || !bits_out || n_bits == 0) return TFFT_E_INVALID;
-    return batch_host(c, false, n_images, rgb, w, h, center, bins, nullptr, n_bits, alpha, 0, 0, 0, nullptr, nullptr, bits_out);
+    const ChunkArgs a = ChunkArgs::list(bins, n_bits, alpha);
+    HostIO io; io.rgb = rgb; io.bits_out = bits_out;
+    return batch_host(c, false, n_images, w, h, center, a, io);
 }
 int tfft_embed_stream_batch(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int h, int center, const tfft_bin* bins, uint64_t n_bins,
                             const uint8_t* header, const uint8_t* payload, uint64_t payload_len, double alpha, double rmin, double rmax,
                             double magmin, uint64_t* usable_out, uint8_t* rgb_out) {
     if (!c || n_images < 0 || !rgb || !rgb_out || !bins || !header || (payload_len && !payload) || n_bins == 0) return TFFT_E_INVALID;
-    if (n_bins < 912 || payload_len > (n_bins - 912) / 56) return TFFT_E_INVALID;      // the walk is shorter than the stream (no wrap for huge lengths)
-    StreamIO io; io.header_in = header; io.payload_in = payload; io.plen = payload_len;
-    return batch_host(c, true, n_images, rgb, w, h, center, bins, nullptr, n_bins, alpha, rmin, rmax, magmin, usable_out, rgb_out, nullptr, &io);
+    if (!stream_fits(n_bins, payload_len)) return TFFT_E_INVALID;      // the walk is shorter than the stream
+    const ChunkArgs a = ChunkArgs::list(bins, n_bins, alpha).capacity(rmin, rmax, magmin).frames(nullptr, nullptr, payload_len);
+    HostIO io; io.rgb = rgb; io.usable = usable_out; io.rgb_out = rgb_out;
+    io.framed = true; io.header_in = header; io.payload_in = payload;
+    return batch_host(c, true, n_images, w, h, center, a, io);
 }
 int tfft_extract_stream_batch(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int h, int center, const tfft_bin* bins, uint64_t n_bins,
                               double alpha, uint8_t* header_out, uint8_t* payload_out, uint64_t max_payload_len, int32_t* status_out,
                               uint8_t* raw_bits_out) {
     if (!c || n_images < 0 || !rgb || !bins || n_bins == 0 || !header_out || !status_out || (max_payload_len && !payload_out)) return TFFT_E_INVALID;
-    StreamIO io; io.header_out = header_out; io.payload_out = payload_out; io.max_plen = max_payload_len; io.status_out = status_out;
-    return batch_host(c, false, n_images, rgb, w, h, center, bins, nullptr, n_bins, alpha, 0, 0, 0, nullptr, nullptr, raw_bits_out, &io);
+    const ChunkArgs a = ChunkArgs::list(bins, n_bins, alpha);
+    HostIO io; io.rgb = rgb; io.bits_out = raw_bits_out;
+    io.framed = true; io.header_out = header_out; io.payload_out = payload_out; io.max_plen = max_payload_len; io.status_out = status_out;
+    return batch_host(c, false, n_images, w, h, center, a, io);
 }
 // ---------------------------------------------------------------- one walk per image (own keys, cover-dependent paths)
 // The shared-list pipelines above with the lists, jitter and adaptive alpha per image: the buckets are built for the chunk's own lists on
@@ -2180,31 +2210,12 @@ int tfft_embed_stream_batch_walks_dev(tfft_ctx* c, int n_images, const void* rgb
     if (!c || !rgb_dev || !rgb_out_dev || !bins_dev || !header_dev || (payload_len && !payload_dev)) return TFFT_E_INVALID;
     int rc = walks_args_ok(c, n_images, n_bins, alpha, adaptive, false);
     if (rc) return rc;
-    if (n_bins < 912 || payload_len > (n_bins - 912) / 56) return TFFT_E_INVALID;      // (before the multiplication: a huge length must not wrap)
-    const uint64_t n_bits = 38ull * 24 + payload_len * 56;           // S:986-995
-    const size_t img_bytes = (size_t)w * h * 3;
-    int32_t* bx = bx_begin(c, n_images, usable_out_dev);
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
-        rc = batch_geometry(c, g, w, h, center);
-        if (rc) return rc;
-        const uint8_t* cov = (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes;
-        if (bx && c->bx_mode) { cov = bx_keep_covers(c, g, cov, (const uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes, img_bytes, c->stream, &rc); if (rc) return rc; }
-        int h1 = 0;
-        rc = split_fork(c, g, &h1);
-        if (rc) return rc;
-        for (int part = 0; part < (h1 ? 2 : 1); part++) {
-            const int s0 = part ? h1 : 0, gp = h1 ? (part ? g - h1 : h1) : g, i1 = i0 + s0;
-            const FrameSrc fr{(const uint8_t*)header_dev + (size_t)i1 * 38, (const uint8_t*)payload_dev + (size_t)i1 * payload_len, payload_len};
-            const WalkSrc ws{jitter_dev ? (const float*)jitter_dev + (size_t)i1 * n_bins : nullptr, adaptive ? 1 : 0};
-            rc = embed_chunk(c, s0, gp, (const uint8_t*)rgb_dev + (size_t)i1 * img_bytes, (const tfft_bin*)bins_dev + (size_t)i1 * n_bins, nullptr,
-                             n_bins, alpha, rmin, rmax, magmin, usable_out_dev ? (unsigned long long*)usable_out_dev + i1 : nullptr,
-                             (uint8_t*)rgb_out_dev + (size_t)i1 * img_bytes, part ? c->stream2 : c->stream, n_bits, &fr, &ws);
-            if (rc) return rc;
-        }
-        if (h1) { rc = split_join(c); if (rc) return rc; }
-        if (bx) { rc = bx_settle(c, 0, g, cov, rmin, rmax, magmin, n_bits, (unsigned long long*)usable_out_dev + i0, bx + i0, c->stream); if (rc) return rc; }
-    }
+    if (!stream_fits(n_bins, payload_len)) return TFFT_E_INVALID;
+    const ChunkArgs a = ChunkArgs::list(bins_dev, n_bins, alpha).capacity(rmin, rmax, magmin).frames(header_dev, payload_dev, payload_len)
+                            .walks(jitter_dev, adaptive);
+    const EmbedDev e{a, (const uint8_t*)rgb_dev, (uint8_t*)rgb_out_dev, (unsigned long long*)usable_out_dev, bx_begin(c, n_images, usable_out_dev)};
+    rc = embed_chunks(c, n_images, w, h, center, true, e);
+    if (rc) return rc;
     return n_images ? check_err_flag(c) : TFFT_OK;
 }
 
@@ -2214,30 +2225,20 @@ int tfft_extract_stream_batch_walks_dev(tfft_ctx* c, int n_images, const void* r
     if (!c || !rgb_dev || !bins_dev || !header_out_dev || !status_out_dev || (max_payload_len && !payload_out_dev)) return TFFT_E_INVALID;
     int rc = walks_args_ok(c, n_images, n_bins, alpha, adaptive, true);
     if (rc) return rc;
-    if (!raw_bits_out_dev) { rc = ensure_stream(c, n_bins); if (rc) return rc; }
-    else if (!c->stream_plen && dev_alloc(c, (void**)&c->stream_plen, (size_t)c->n_slots * sizeof(unsigned))) return TFFT_E_NOMEM;
-    const size_t img_bytes = (size_t)w * h * 3;
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
-        rc = batch_geometry(c, g, w, h, center);
-        if (rc) return rc;
-        int h1 = 0;
-        rc = split_fork(c, g, &h1);
-        if (rc) return rc;
-        for (int part = 0; part < (h1 ? 2 : 1); part++) {
-            const int s0 = part ? h1 : 0, gp = h1 ? (part ? g - h1 : h1) : g, i1 = i0 + s0;
-            hipStream_t st = part ? c->stream2 : c->stream;
-            // every position of the image's own walk is read in the pass that has the spectrum on chip, then the header decides (S:1223-1264)
-            uint8_t* raw = raw_bits_out_dev ? (uint8_t*)raw_bits_out_dev + (size_t)i1 * n_bins : c->stream_bits + (size_t)s0 * n_bins;
-            const WalkSrc ws{jitter_dev ? (const float*)jitter_dev + (size_t)i1 * n_bins : nullptr, adaptive ? 1 : 0};
-            rc = extract_chunk(c, s0, gp, (const uint8_t*)rgb_dev + (size_t)i1 * img_bytes, (const tfft_bin*)bins_dev + (size_t)i1 * n_bins, n_bins, alpha,
-                               raw, st, &ws);
-            if (rc) return rc;
-            HIPCHK(c, launch_stream_decode(raw, n_bins, max_payload_len, gp, (uint8_t*)header_out_dev + (size_t)i1 * 38,
-                                           (uint8_t*)payload_out_dev + (size_t)i1 * max_payload_len, (int*)status_out_dev + i1, c->stream_plen + s0, st));
-        }
-        if (h1) { rc = split_join(c); if (rc) return rc; }
-    }
+    rc = ensure_stream(c, n_bins, !raw_bits_out_dev);
+    if (rc) return rc;
+    const uint8_t* rgb = (const uint8_t*)rgb_dev;
+    uint8_t* raw_out = (uint8_t*)raw_bits_out_dev;
+    const size_t img_bytes = image_bytes(w, h);
+    const DecodeOut out{(uint8_t*)header_out_dev, (uint8_t*)payload_out_dev, max_payload_len, (int*)status_out_dev};
+    const ChunkArgs a = ChunkArgs::list(bins_dev, n_bins, alpha).walks(jitter_dev, adaptive);
+    rc = for_chunks(c, n_images, w, h, center, true, nullptr, [&](const Chunk& k) {
+        // (each half of a split chunk has the scratch of its own slots)
+        uint8_t* raw = raw_out ? nth(raw_out, k.i1, n_bins) : c->stream_bits + (size_t)k.s0 * n_bins;
+        const int rc1 = extract_chunk(c, k.s0, k.g, k.st, a.from(k.i1), nth(rgb, k.i1, img_bytes), raw);
+        return rc1 ? rc1 : decode_chunk(c, k, raw, n_bins, out, c->stream_plen + k.s0);
+    });
+    if (rc) return rc;
     return n_images ? check_err_flag(c) : TFFT_OK;
 }
 
@@ -2247,10 +2248,11 @@ int tfft_embed_stream_batch_walks(tfft_ctx* c, int n_images, const uint8_t* rgb,
     if (!c || !rgb || !rgb_out || !bins || !header || (payload_len && !payload)) return TFFT_E_INVALID;
     int rc = walks_args_ok(c, n_images, n_bins, alpha, adaptive, false);
     if (rc) return rc;
-    if (n_bins < 912 || payload_len > (n_bins - 912) / 56) return TFFT_E_INVALID;
-    StreamIO io; io.header_in = header; io.payload_in = payload; io.plen = payload_len;
-    const WalkSrc ws{jitter, adaptive ? 1 : 0};
-    return batch_host(c, true, n_images, rgb, w, h, center, bins, nullptr, n_bins, alpha, rmin, rmax, magmin, usable_out, rgb_out, nullptr, &io, &ws);
+    if (!stream_fits(n_bins, payload_len)) return TFFT_E_INVALID;
+    const ChunkArgs a = ChunkArgs::list(bins, n_bins, alpha).capacity(rmin, rmax, magmin).frames(nullptr, nullptr, payload_len).walks(jitter, adaptive);
+    HostIO io; io.rgb = rgb; io.usable = usable_out; io.rgb_out = rgb_out;
+    io.framed = true; io.header_in = header; io.payload_in = payload;
+    return batch_host(c, true, n_images, w, h, center, a, io);
 }
 int tfft_extract_stream_batch_walks(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int h, int center, const tfft_bin* bins, const float* jitter,
                                     uint64_t n_bins, int adaptive, double alpha, uint8_t* header_out, uint8_t* payload_out, uint64_t max_payload_len,
@@ -2258,9 +2260,10 @@ int tfft_extract_stream_batch_walks(tfft_ctx* c, int n_images, const uint8_t* rg
     if (!c || !rgb || !bins || !header_out || !status_out || (max_payload_len && !payload_out)) return TFFT_E_INVALID;
     int rc = walks_args_ok(c, n_images, n_bins, alpha, adaptive, true);
     if (rc) return rc;
-    StreamIO io; io.header_out = header_out; io.payload_out = payload_out; io.max_plen = max_payload_len; io.status_out = status_out;
-    const WalkSrc ws{jitter, adaptive ? 1 : 0};
-    return batch_host(c, false, n_images, rgb, w, h, center, bins, nullptr, n_bins, alpha, 0, 0, 0, nullptr, nullptr, raw_bits_out, &io, &ws);
+    const ChunkArgs a = ChunkArgs::list(bins, n_bins, alpha).walks(jitter, adaptive);
+    HostIO io; io.rgb = rgb; io.bits_out = raw_bits_out;
+    io.framed = true; io.header_out = header_out; io.payload_out = payload_out; io.max_plen = max_payload_len; io.status_out = status_out;
+    return batch_host(c, false, n_images, w, h, center, a, io);
 }
 
 // ---------------------------------------------------------------- fitted embed: stego that survives the crop
@@ -2283,11 +2286,10 @@ static int ensure_fit(tfft_ctx* c, uint64_t n_bins) {
             dev_alloc(c, (void**)&c->fit_wrong, (size_t)c->n_slots * sizeof(uint32_t))) return TFFT_E_NOMEM;
     }
     if (c->fit_d && need <= c->fit_cap) return TFFT_OK;
-    (void)hipStreamSynchronize(c->stream);
-    invalidate_graphs(c);
-    (void)hipFree(c->fit_d); (void)hipFree(c->fit_mu); c->fit_d = nullptr; c->fit_mu = nullptr; c->fit_cap = 0;
-    const uint64_t cap = need + need / 4 + 1024;
-    if (dev_alloc(c, (void**)&c->fit_d, cap * sizeof(float2)) || dev_alloc(c, (void**)&c->fit_mu, cap * sizeof(float))) return TFFT_E_NOMEM;
+    c->fit_cap = 0;
+    const uint64_t cap = grown(need, 1024);
+    int rc = regrow(c, {{(void**)&c->fit_d, cap * sizeof(float2)}, {(void**)&c->fit_mu, cap * sizeof(float)}});
+    if (rc) return rc;
     c->fit_cap = cap;
     return TFFT_OK;
 }
@@ -2296,8 +2298,8 @@ static int ensure_fit(tfft_ctx* c, uint64_t n_bins) {
 // when the |F|^2 store is available to switch off)
 static int fit_forward(tfft_ctx* c, int g, const uint8_t* rgb, hipStream_t st) {
     auto& tb = c->tb[0];
-    ColParams em{};
-    em.rd_bins = tb.ent; em.rd_off = tb.off; em.trash = c->trash; em.em_fl = tb.fl; em.em_pb = tb.pb; em.em_n = 0; em.rd_walks = 1;
+    ColParams em = bucketed_params(c, 0);
+    em.em_fl = tb.fl; em.em_pb = tb.pb; em.em_n = 0; em.rd_walks = 1;
     if (c->stats_m2) { em.em_m2 = 2; em.st_col0 = c->col0_pool; }
     StageMode md; md.fwd_emit = &em;
     return enqueue_forward(c, 0, g, rgb, st, md);
@@ -2305,37 +2307,37 @@ static int fit_forward(tfft_ctx* c, int g, const uint8_t* rgb, hipStream_t st) {
 
 // One chunk of g <= n_slots images in slots [0, g), on the context's stream.  cover: the chunk's covers in buffers nothing writes during
 // the call; iters: host, g entries; wrong_dev: device, g entries
-static int fit_chunk(tfft_ctx* c, int g, const uint8_t* cover, const tfft_bin* bins, const float* jit, uint64_t n_bins, int adaptive,
-                     const FrameSrc& fr, uint64_t n_bits, double alpha, double rmin, double rmax, double magmin, unsigned long long* usable,
-                     int max_iters, double margin, uint8_t* rgb_out, int32_t* iters, uint32_t* wrong_dev) {
+static int fit_chunk(tfft_ctx* c, int g, const ChunkArgs& a, const uint8_t* cover, unsigned long long* usable, int max_iters, double margin,
+                     uint8_t* rgb_out, int32_t* iters, uint32_t* wrong_dev) {
     hipStream_t st = c->stream;
     const Slot& s = c->slots[0];
-    const WalkSrc ws{jit, adaptive ? 1 : 0};
+    const tfft_bin* bins = a.bins;
+    const float* jit = a.jit;
+    const uint64_t n_bins = a.n_bits;
     // iteration 0: the walks embed itself (bucket build, bit and jitter gathers, forward with statistics and capacities, COLS_EMIT of F0)
-    int rc = embed_chunk(c, 0, g, cover, bins, nullptr, n_bins, alpha, rmin, rmax, magmin, usable, rgb_out, st, n_bits, &fr, &ws);
+    int rc = embed_chunk(c, 0, g, st, a, cover, usable, rgb_out);
     if (rc) return rc;
     rc = check_err_flag(c);         // (a bin out of range: the buckets do not describe the lists)
     if (rc) return rc;
     auto& tb = c->tb[0];
     if (!c->embed_delta) {          // TFFT_EMBED_DELTA=0 wrote F' into the spectrum: no buckets, no F0 in bucket order yet
-        const ColPlan pl = plan_cols(c, s.PH, s.PWi, g);
-        const int G = pl.direct ? 1 : (1 << pl.log_n1), ntiles = (s.PWi / 2 + 15) / 16;
-        rc = ensure_buckets(c, 0, n_bins, 3 * ntiles * G, true);
-        if (!rc) rc = build_buckets_walks(c, 0, bins, n_bins, g, s, G, jit, st);
+        const BucketGeom bg = bucket_geom(c, s, g);
+        rc = ensure_buckets(c, 0, n_bins, bg.nb, true);
+        if (!rc) rc = build_buckets_walks(c, 0, bins, n_bins, g, s, bg, jit, st);
         if (rc) return rc;
-        HIPCHK(c, launch_gather_bits_walks(tb.ent, nullptr, fr.hdr, fr.pay, fr.plen, n_bins, n_bits, g, tb.pb, st));
+        HIPCHK(c, launch_gather_bits_walks(tb.ent, nullptr, a.hdr, a.pay, a.plen, n_bins, a.limit, g, tb.pb, st));
         rc = fit_forward(c, g, cover, st);
         if (rc) return rc;
     }
     const float2* jp = jit ? tb.jp : nullptr;
     const double sigma = sqrt((double)s.W * (double)s.H / 24.0);
-    HIPCHK(c, launch_fit_init(tb.ent, tb.fl, tb.pb, jp, bins, adaptive ? c->med : nullptr, n_bins, g, alpha, margin, TFFT_FIT_KAPPA * sigma,
+    HIPCHK(c, launch_fit_init(tb.ent, tb.fl, tb.pb, jp, bins, a.adaptive ? c->med : nullptr, n_bins, g, a.alpha, margin, TFFT_FIT_KAPPA * sigma,
                               c->fit_d, c->fit_mu, st));
     // a correction of a bin reaches the cropped image with W*H/(PW*PH) of its energy
     const double gain = ((double)s.PW * (double)s.PH) / ((double)s.W * (double)s.H);
     const unsigned nblk = (unsigned)std::min<uint64_t>(kFitMaxBlocks, (n_bins + 1023) / 1024);
-    ColParams ed{};
-    ed.rd_bins = tb.ent; ed.rd_off = tb.off; ed.trash = c->trash; ed.em_fl = c->fit_d; ed.em_pb = tb.pb; ed.em_n = 0; ed.rd_walks = 1; ed.em_dsrc = 1;
+    ColParams ed = bucketed_params(c, 0);
+    ed.em_fl = c->fit_d; ed.em_pb = tb.pb; ed.em_n = 0; ed.rd_walks = 1; ed.em_dsrc = 1;
     std::vector<unsigned> cnt((size_t)2 * g);
     for (int i = 0; i < g; i++) iters[i] = -1;
     for (int t = 0;; t++) {
@@ -2364,7 +2366,7 @@ static int fit_args_ok(const tfft_ctx* c, int n_images, uint64_t n_bins, uint64_
     int rc = walks_args_ok(c, n_images, n_bins, alpha, adaptive, false);
     if (rc) return rc;
     if (!(alpha > 0.0 && alpha < M_PI / 2) || max_iters < 0 || !(margin > 0.0)) return TFFT_E_INVALID;      // the line-side reading needs 0 < alpha < pi/2
-    if (n_bins < 912 || payload_len > (n_bins - 912) / 56) return TFFT_E_INVALID;
+    if (!stream_fits(n_bins, payload_len)) return TFFT_E_INVALID;
     return TFFT_OK;
 }
 
@@ -2377,22 +2379,23 @@ int tfft_embed_stream_batch_fit_dev(tfft_ctx* c, int n_images, const void* rgb_d
     if (rc) return rc;
     rc = ensure_fit(c, n_bins);
     if (rc) return rc;
-    const uint64_t n_bits = 38ull * 24 + payload_len * 56;           // S:986-995
+    const ChunkArgs a = ChunkArgs::list(bins_dev, n_bins, alpha).capacity(rmin, rmax, magmin).frames(header_dev, payload_dev, payload_len)
+                            .walks(jitter_dev, adaptive);
     const size_t img_bytes = (size_t)w * h * 3;
     std::vector<int32_t> iters((size_t)c->n_slots);
     int32_t* bx = bx_begin(c, n_images, usable_out_dev);
+    // (Not for_chunks: the fit copies every chunk's covers whether or not the capacities are settled, settles against that copy, and
+    // uploads the iteration counts after the settling -- the driver would have to learn all three.)
     for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
         const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
         rc = batch_geometry(c, g, w, h, center);
         if (rc) return rc;
         // every iteration adds to the ORIGINAL covers: the chunk's own copy in the slots' image buffers (rgb_out may be rgb)
         HIPCHK(c, hipMemcpyAsync(c->img(0), (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyDeviceToDevice, c->stream));
-        const FrameSrc fr{(const uint8_t*)header_dev + (size_t)i0 * 38, (const uint8_t*)payload_dev + (size_t)i0 * payload_len, payload_len};
-        rc = fit_chunk(c, g, c->img(0), (const tfft_bin*)bins_dev + (size_t)i0 * n_bins, jitter_dev ? (const float*)jitter_dev + (size_t)i0 * n_bins : nullptr,
-                       n_bins, adaptive, fr, n_bits, alpha, rmin, rmax, magmin, usable_out_dev ? (unsigned long long*)usable_out_dev + i0 : nullptr,
-                       max_iters, margin, (uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes, iters.data(), wrong_out_dev ? (uint32_t*)wrong_out_dev + i0 : nullptr);
+        rc = fit_chunk(c, g, a.from(i0), c->img(0), usable_out_dev ? (unsigned long long*)usable_out_dev + i0 : nullptr, max_iters, margin,
+                       (uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes, iters.data(), wrong_out_dev ? (uint32_t*)wrong_out_dev + i0 : nullptr);
         if (rc) return rc;
-        if (bx) { rc = bx_settle(c, 0, g, c->img(0), rmin, rmax, magmin, n_bits, (unsigned long long*)usable_out_dev + i0, bx + i0, c->stream); if (rc) return rc; }
+        if (bx) { rc = bx_settle(c, 0, g, c->img(0), a, (unsigned long long*)usable_out_dev + i0, bx + i0, c->stream); if (rc) return rc; }
         if (iters_out_dev) {
             HIPCHK(c, hipMemcpyAsync((int32_t*)iters_out_dev + i0, iters.data(), (size_t)g * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));      // (the host array is reused by the next chunk)
@@ -2414,7 +2417,9 @@ int tfft_embed_stream_batch_fit(tfft_ctx* c, int n_images, const uint8_t* rgb, i
     if (!rc) rc = ensure_stream_io(c, payload_len);
     if (!rc) rc = ensure_fit(c, n_bins);
     if (rc) return rc;
-    const uint64_t n_bits = 38ull * 24 + payload_len * 56;
+    // (every chunk goes through the front of the staging buffers)
+    const ChunkArgs a = ChunkArgs::list(c->stage_bins, n_bins, alpha).capacity(rmin, rmax, magmin).frames(c->sio_hdr, c->sio_pay, payload_len)
+                            .walks(jitter ? c->stage_jit : nullptr, adaptive);
     const size_t img_bytes = (size_t)w * h * 3;
     std::vector<int32_t> iters((size_t)c->n_slots);
     int32_t* bx = bx_begin(c, n_images, usable_out);
@@ -2426,13 +2431,11 @@ int tfft_embed_stream_batch_fit(tfft_ctx* c, int n_images, const uint8_t* rgb, i
         HIPCHK(c, hipMemcpyAsync(c->img(0), rgb + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemcpyAsync(c->stage_bins, bins + (size_t)i0 * n_bins, (size_t)g * n_bins * sizeof(tfft_bin), hipMemcpyHostToDevice, st));
         if (jitter) HIPCHK(c, hipMemcpyAsync(c->stage_jit, jitter + (size_t)i0 * n_bins, (size_t)g * n_bins * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->sio_hdr, header + (size_t)i0 * 38, (size_t)g * 38, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->sio_hdr, header + (size_t)i0 * kHeaderBytes, (size_t)g * kHeaderBytes, hipMemcpyHostToDevice, st));
         if (payload_len) HIPCHK(c, hipMemcpyAsync(c->sio_pay, payload + (size_t)i0 * payload_len, (size_t)g * payload_len, hipMemcpyHostToDevice, st));
-        const FrameSrc fr{c->sio_hdr, c->sio_pay, payload_len};
-        rc = fit_chunk(c, g, c->img(0), (const tfft_bin*)c->stage_bins, jitter ? (const float*)c->stage_jit : nullptr, n_bins, adaptive, fr, n_bits,
-                       alpha, rmin, rmax, magmin, usable_out ? c->usable : nullptr, max_iters, margin, c->out_pool, iters.data(), c->fit_wrong);
+        rc = fit_chunk(c, g, a, c->img(0), usable_out ? c->usable : nullptr, max_iters, margin, c->out_pool, iters.data(), c->fit_wrong);
         if (rc) return rc;
-        if (bx) { rc = bx_settle(c, 0, g, c->img(0), rmin, rmax, magmin, n_bits, c->usable, bx + i0, st); if (rc) return rc; }
+        if (bx) { rc = bx_settle(c, 0, g, c->img(0), a, c->usable, bx + i0, st); if (rc) return rc; }
         HIPCHK(c, hipMemcpyAsync(rgb_out + (size_t)i0 * img_bytes, c->out_pool, (size_t)g * img_bytes, hipMemcpyDeviceToHost, st));
         if (usable_out) HIPCHK(c, hipMemcpyAsync(usable_out + i0, c->usable, (size_t)g * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         if (wrong_out) HIPCHK(c, hipMemcpyAsync(wrong_out + i0, c->fit_wrong, (size_t)g * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -2465,12 +2468,13 @@ int tfft_lowfreq_mag_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, i
 // ---- stego analysis: annulus phase histograms, cover / stego quality
 }  // extern "C"
 namespace {
-// the analysis scratch (partials of one chunk, then the host forms' results): grown on demand; an earlier call may still read it
+// the analysis scratch (partials of one chunk, then the host forms' results): grown on demand; an earlier call may still read it.
+// (Like bx_value_buffers, no quiesce(): the analysis calls run on the context's stream alone and are never captured.)
 int ensure_analysis(tfft_ctx* c, size_t bytes) {
     if (c->an_buf && bytes <= c->an_cap) return TFFT_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     (void)hipFree(c->an_buf); c->an_buf = nullptr; c->an_cap = 0;
-    const size_t cap = bytes + bytes / 4 + 4096;
+    const size_t cap = grown(bytes, 4096);
     int rc = dev_alloc(c, &c->an_buf, cap);
     if (rc) return rc;
     c->an_cap = cap;
@@ -2631,7 +2635,7 @@ int tfft_frame_expand_dev(tfft_ctx* c, int n_images, const void* header_dev, con
     if (!c || n_images < 0 || !header_dev || (payload_len && !payload_dev) || !bits_out_dev) return TFFT_E_INVALID;
     if (n_images == 0) return TFFT_OK;
     HIPCHK(c, launch_frame_expand((const uint8_t*)header_dev, (const uint8_t*)payload_dev, payload_len, n_images, (uint8_t*)bits_out_dev,
-                                  38ull * 24 + payload_len * 56, c->stream));
+                                  stream_bits(payload_len), c->stream));
     return TFFT_OK;
 }
 int tfft_frame_majority_dev(tfft_ctx* c, int n_images, const void* bits_dev, uint64_t payload_len, void* header_out_dev,
@@ -2680,17 +2684,18 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
     if (n_launches) *n_launches = launches;
     *ms_per_rep = 0.f;
     if (launches == 0) return TFFT_OK;
+    const BucketGeom bg = bucket_geom(c, s, n_images);      // (as embed_chunk and extract_chunk bucket the list)
     { const float2* t; int rc = get_twiddles(c, s.PWi, &t); if (rc) return rc; rc = get_twiddles(c, s.PH, &t); if (rc) return rc; }
     ColParams rd{};
     if (stage == COLS_FWD_READ) {
         if (!bins_dev || !index_ok(c, n_bits)) return TFFT_E_INVALID;
         if (c->tile_read && n_bits > 0 && (n_images >= 8 || c->tile_read >= 2)) {
             if (!bits_out_dev) return TFFT_E_INVALID;
-            const int G = pl.direct ? 1 : (1 << pl.log_n1), ntiles = (s.PWi / 2 + 15) / 16;
-            int rc = ensure_buckets(c, 0, n_bits, 3 * ntiles * G);
+            int rc = ensure_buckets(c, 0, n_bits, bg.nb);
             if (rc) return rc;
-            HIPCHK(c, launch_bucket_bins((const tfft_bin*)bins_dev, c->bit_index, n_bits, s.PH, s.PWi, G, c->tb[0].cnt, c->tb[0].off, c->tb[0].ent, c->err, c->tile_read == 2, c->stream));
-            rd.rd_bins = c->tb[0].ent; rd.rd_off = c->tb[0].off; rd.rd_bits = (uint8_t*)bits_out_dev; rd.rd_n = n_bits; rd.trash = c->trash;
+            HIPCHK(c, launch_bucket_bins((const tfft_bin*)bins_dev, c->bit_index, n_bits, s.PH, s.PWi, bg.G, c->tb[0].cnt, c->tb[0].off, c->tb[0].ent, c->err, c->tile_read == 2, c->stream));
+            rd = bucketed_params(c, 0);
+            rd.rd_bits = (uint8_t*)bits_out_dev; rd.rd_n = n_bits;
         } else {
             HIPCHK(c, launch_bins_last_row((const tfft_bin*)bins_dev, n_bits, s.PH, s.PWi, c->last_row, c->stream));
         }
@@ -2698,13 +2703,13 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
     ColParams em{};
     if ((stage == COLS_INV_A || stage == final_fwd || stage == EMBED || (stage == MEDIANS && tile)) && delta && bits_dev) {
         if (!index_ok(c, n_bits)) return TFFT_E_STATE;
-        const int G = pl.direct ? 1 : (1 << pl.log_n1), ntiles = (s.PWi / 2 + 15) / 16;
-        int rc = ensure_buckets(c, 0, n_bits, 3 * ntiles * G, true);
+        int rc = ensure_buckets(c, 0, n_bits, bg.nb, true);
         if (rc) return rc;
-        rc = build_buckets(c, 0, (const tfft_bin*)bins_dev, n_bits, s, G, c->stream);
+        rc = build_buckets(c, 0, (const tfft_bin*)bins_dev, n_bits, s, bg.G, c->stream);
         if (rc) return rc;
         const EmbedParams ep0 = embed_params(c, s, n_bits, alpha, 0, nullptr, false);
-        em.rd_bins = c->tb[0].ent; em.rd_off = c->tb[0].off; em.trash = c->trash; em.em_fl = c->tb[0].fl; em.em_pb = c->tb[0].pb; em.em_n = n_bits;
+        em = bucketed_params(c, 0);
+        em.em_fl = c->tb[0].fl; em.em_pb = c->tb[0].pb; em.em_n = n_bits;
         em.em_cos = ep0.cos_a; em.em_sin = ep0.sin_a;
         if (m2) { em.em_m2 = 1; em.st_col0 = c->col0_pool; }
     }
@@ -2753,8 +2758,7 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
             case EMBED: {
                 if (!index_ok(c, n_bits)) return TFFT_E_STATE;
                 if (em.rd_bins) {      // delta embedding: what is left of the embed stage is the gather of the stream bits into bucket order
-                    const int G = pl.direct ? 1 : (1 << pl.log_n1), nb = 3 * ((s.PWi / 2 + 15) / 16) * G;
-                    HIPCHK(c, launch_gather_bits(c->tb[0].ent, c->tb[0].off + nb, (const uint8_t*)bits_dev, nullptr, nullptr, 0, n_bits, n_bits, n_images, c->tb[0].pb, c->stream));
+                    HIPCHK(c, launch_gather_bits(c->tb[0].ent, c->tb[0].off + bg.nb, (const uint8_t*)bits_dev, nullptr, nullptr, 0, n_bits, n_bits, n_images, c->tb[0].pb, c->stream));
                     break;
                 }
                 EmbedParams ep = embed_params(c, s, n_bits, alpha, 0, nullptr, false);
@@ -2768,18 +2772,12 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
                 break;
             }
             case MEDIANS:
-                if (c->stats_fused) {
-                    CapParams p = cap_params(c, s, 0.05, 0.45);
-                    p.magmin = 0.01;
-                    rc = enqueue_medians(c, 0, n_images, c->stream, &p, c->usable, m2);
-                } else rc = enqueue_medians(c, 0, n_images, c->stream);
+                if (c->stats_fused) rc = enqueue_medians(c, 0, n_images, c->stream, &tcap, c->usable, m2);
+                else rc = enqueue_medians(c, 0, n_images, c->stream);
                 break;
-            case CAPACITY: {
-                CapParams p = cap_params(c, s, 0.05, 0.45);
-                p.magmin = 0.01;
-                HIPCHK(c, launch_capacity(c->spec(0), p, n_images, c->med, c->partial, c->usable, c->stream));
+            case CAPACITY:
+                HIPCHK(c, launch_capacity(c->spec(0), tcap, n_images, c->med, c->partial, c->usable, c->stream));
                 break;
-            }
             default: rc = enqueue_fft_stage(c, 0, n_images, stage, (const uint8_t*)rgb_dev, (uint8_t*)rgb_out_dev, c->stream);
         }
         if (rc) return rc;
