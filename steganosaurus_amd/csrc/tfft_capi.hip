@@ -1,6 +1,6 @@
 // tfft_capi.hip -- context management and the C ABI of libturtlefft_hip.so
 // (include/turtlefft_hip.h).  Host C++ only; all device work is in
-// tfft_kernels.hip.  There is deliberately no CPU fallback in this file: every
+// tfft_kernels.hip, tfft_stats.hip, tfft_exact.hip and tfft_audit64.hip.  There is deliberately no CPU fallback in this file: every
 // entry point that computes needs a live gfx950 context.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -482,6 +482,18 @@ static int stats_clean_if_dirty(tfft_ctx* c, hipStream_t st) {
     c->stats_dirty = false;
     return TFFT_OK;
 }
+// the statistics' buffers of slots [s0, s0+n), capacities -> usable.  (The batch capacity keeps its partial counts and flags in ONE region
+// per call: the slots use the start of the pool's share of the compute stream -- s0 is 0 or the second half of a two-stream chunk: shares do
+// not overlap for n <= n_slots - s0)
+static float2* stat_col0(tfft_ctx* c, int s0) { return c->col0_pool + (size_t)s0 * 3 * c->slots[s0].PH; }
+static unsigned* stat_partial(tfft_ctx* c, int s0) { return c->partial + (size_t)s0 * (3 * TFFT_STAT_MAX_BLOCKS + 1); }
+static StatBufs stat_bufs(tfft_ctx* c, int s0, unsigned long long* usable) {
+    return StatBufs{c->sel + 3 * s0, c->cand_pool + (size_t)3 * s0 * c->cand_stride, c->cand_stride, c->med + 3 * s0,
+                    stat_partial(c, s0), c->amb + (size_t)3 * s0 * TFFT_AMB_CAP, usable, stat_col0(c, s0)};
+}
+static StatOpts stat_opts(const tfft_ctx* c, const CapParams* cap, bool m2) {
+    return StatOpts{cap, m2, c->stats_compact, c->median_force_fallback, c->stats_skew, c->n_cus, c->collect_resident};
+}
 static int enqueue_medians_impl(tfft_ctx* c, int s0, int n, hipStream_t st, const CapParams* cap, unsigned long long* usable, bool m2);
 int enqueue_medians(tfft_ctx* c, int s0, int n, hipStream_t st, const CapParams* cap = nullptr, unsigned long long* usable = nullptr, bool m2 = false) {
     int rc = stats_clean_if_dirty(c, st);
@@ -491,19 +503,13 @@ int enqueue_medians(tfft_ctx* c, int s0, int n, hipStream_t st, const CapParams*
 }
 static int enqueue_medians_impl(tfft_ctx* c, int s0, int n, hipStream_t st, const CapParams* cap, unsigned long long* usable, bool m2) {
     const Slot& s = c->slots[s0];
-    // the batch capacity keeps its partial counts and flags in ONE region per call: slots [s0, s0+n) use the start of the pool's
-    // share of the compute stream (s0 is 0 or the second half of a two-stream chunk: shares do not overlap for n <= n_slots - s0)
-    unsigned* partial = c->partial + (size_t)s0 * (3 * TFFT_STAT_MAX_BLOCKS + 1);
-    HIPCHK(c, launch_medians(c->spec(s0), s.PH, s.PWi, c->slot_stride, n, c->sel + 3 * s0,
-                             c->cand_pool + (size_t)3 * s0 * c->cand_stride, c->cand_stride, c->med + 3 * s0, c->median_force_fallback, c->n_cus, c->collect_resident, st,
-                             cap, partial, c->amb + (size_t)3 * s0 * TFFT_AMB_CAP, usable, c->stats_compact,
-                             m2 ? c->col0_pool + (size_t)s0 * 3 * s.PH : nullptr, c->stats_skew));
+    HIPCHK(c, launch_medians(c->spec(s0), s.PH, s.PWi, c->slot_stride, n, stat_bufs(c, s0, usable), stat_opts(c, cap, m2), st));
     return TFFT_OK;
 }
 // the batched delta embeds with capacity: may the last forward step store |F|^2 instead of the spectrum?
 static bool stats_m2_applies(const tfft_ctx* c, const Slot& s, const CapParams& p) {
     return c->stats_m2 && c->stats_fused && c->stats_compact && !c->median_force_fallback && p.bw > 0 &&
-           (unsigned long long)s.PH * s.PWi <= (1ull << 24);
+           (unsigned long long)s.PH * s.PWi <= TFFT_COMPACT_MAX_BINS;
 }
 
 int ensure_stage(tfft_ctx* c, uint64_t n) {
@@ -1226,7 +1232,7 @@ int tfft_capacity(tfft_ctx* c, int slot, double rmin, double rmax, const double 
         c->ex_last[0] = c->ex_last[1] = c->ex_last[2] = 0;
     }
     HIPCHK(c, launch_capacity(c->spec(slot), p, 1, nullptr, c->partial + (size_t)3 * slot * TFFT_STAT_MAX_BLOCKS,
-                              c->usable + slot, c->stream));
+                              c->usable + slot, c->stream, nullptr));
     unsigned long long u = 0;
     HIPCHK(c, hipMemcpyAsync(&u, c->usable + slot, sizeof u, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1551,7 +1557,7 @@ static bool tilestats_applies(const tfft_ctx* c, const Slot& s, const ColPlan& p
     if (c->stats_tile < 2 && (unsigned long long)n * s.PH * s.PWi < (1ull << 24)) return false;
     const unsigned long long mirror_d = (unsigned long long)(p.PW - s.PWi / 2) * (unsigned long long)(p.PW - s.PWi / 2);
     return p.bw > 0 && p.s_lo <= p.s_hi && p.s_hi < 0xFFFFFFFFull && mirror_d > p.s_hi && !pl.direct && pl.log_n2 >= 4 && pl.log_n2 <= 9 &&
-           (unsigned long long)s.PH * s.PWi <= (1ull << 24) && (s.PWi / 2) % 16 == 0;
+           (unsigned long long)s.PH * s.PWi <= TFFT_COMPACT_MAX_BINS && (s.PWi / 2) % 16 == 0;
 }
 
 // The statistics after COLS_STAT, in two parts so that the first can run beside the inverse transform (embed_chunk):
@@ -1561,8 +1567,7 @@ static bool tilestats_applies(const tfft_ctx* c, const Slot& s, const ColPlan& p
 //           the inverse in between keeps its intermediate in `spec` (StageMode::inv_via_spec)
 static int enqueue_tilestats_select(tfft_ctx* c, int s0, int g, hipStream_t st) {
     const Slot& s = c->slots[s0];
-    HIPCHK(c, launch_stat_select(s.PH, g, c->sel + 3 * s0, c->cand_pool + (size_t)3 * s0 * c->cand_stride, c->cand_stride, c->med + 3 * s0,
-                                 c->col0_pool + (size_t)s0 * 3 * s.PH, st));
+    HIPCHK(c, launch_stat_select(s.PH, g, stat_bufs(c, s0, nullptr), st));
     return TFFT_OK;
 }
 static int enqueue_tilestats_tail(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, hipStream_t st, const CapParams& cap, unsigned long long* usable) {
@@ -1573,8 +1578,7 @@ static int enqueue_tilestats_tail(tfft_ctx* c, int s0, int g, const uint8_t* rgb
     StageMode mg; mg.fwd_plain_extra = &gt;
     int rc = enqueue_fft_stage(c, s0, g, pl.direct ? COLS_FWD_A : COLS_FWD_B, rgb_in, nullptr, st, mg);
     if (rc) return rc;
-    HIPCHK(c, launch_stat_settle(c->spec(s0), s.PH, s.PWi, c->slot_stride, g, c->sel + 3 * s0, c->med + 3 * s0, &cap,
-                                 c->partial + (size_t)s0 * (3 * TFFT_STAT_MAX_BLOCKS + 1), c->amb + (size_t)3 * s0 * TFFT_AMB_CAP, usable, st));
+    HIPCHK(c, launch_stat_settle(c->spec(s0), s.PH, s.PWi, c->slot_stride, g, stat_bufs(c, s0, usable), stat_opts(c, &cap, false), st));
     for (int i = 0; i < g; i++) { c->slots[s0 + i].has_spec = false; c->slots[s0 + i].rgb_src = nullptr; }
     return TFFT_OK;
 }
@@ -1606,28 +1610,23 @@ static int enqueue_forward_tilestats(tfft_ctx* c, int s0, int g, const uint8_t* 
         rc = enqueue_fft_stage(c, s0, g, stage, rgb_in, nullptr, st);
         if (rc) return rc;
     }
-    float2* col0 = c->col0_pool + (size_t)s0 * 3 * s.PH;
-    SelectState* sel = c->sel + 3 * s0;
-    unsigned* partial = c->partial + (size_t)s0 * (3 * TFFT_STAT_MAX_BLOCKS + 1);
-    float* amb = c->amb + (size_t)3 * s0 * TFFT_AMB_CAP;
-    unsigned* cand = c->cand_pool + (size_t)3 * s0 * c->cand_stride;
+    const StatBufs sb = stat_bufs(c, s0, usable);
     // (1) every step-th column tile, transformed and dropped into a histogram of |F|^2 (in LDS, ColParams::hist_sel): its median
     // brackets the plane's.  (First form: the tiles written side by side as a narrow spectrum + k_hist_spec over it -- 0.15 ms of a
     // 32 x 1080p launch where this takes 0.0x.)
     ColParams ex{};
     ex.tile_step = step; ex.tile_off = off; ex.out_M = Ms; ex.out_plane_stride = (size_t)s.PH * Ms; ex.out_img_stride = (size_t)3 * s.PH * Ms;
-    ex.hist_sel = sel; ex.g_step = g_step; ex.g_off = g_step / 2;
+    ex.hist_sel = sb.st; ex.g_step = g_step; ex.g_off = g_step / 2;
     if (phases & 2) {
         StageMode ms;
         ms.fwd_plain_extra = &ex;
         rc = enqueue_fft_stage(c, s0, g, final_fwd, rgb_in, nullptr, st, ms);
         if (rc) return rc;
-        HIPCHK(c, launch_stat_guess(nullptr, s.PH, s.PWi, Ms, ex.out_img_stride, g, sel, &cap, partial, 0, st));
-        if (c->stats_skew) HIPCHK(c, launch_skew_bracket(sel, g, c->stats_skew, st));
+        HIPCHK(c, launch_stat_guess(nullptr, s.PH, s.PWi, Ms, ex.out_img_stride, 0, g, sb, stat_opts(c, &cap, false), st));
     }
     // (2) the last forward step: values of the listed bins + the bracket pass on every value
     if (phases & 4) {
-    em.st_sel = sel; em.st_cand = cand; em.st_cand_stride = c->cand_stride; em.st_partial = partial; em.st_amb = amb; em.st_col0 = col0;
+    em.st_sel = sb.st; em.st_cand = sb.cand; em.st_cand_stride = sb.cand_stride; em.st_partial = sb.partial; em.st_amb = sb.amb; em.st_col0 = sb.col0;
     em.st_slo = cap.s_lo > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)cap.s_lo; em.st_shi = cap.s_hi > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)cap.s_hi;
     em.st_cap = 1; em.st_PW = cap.PW;
     { StageMode me; me.fwd_emit = &em;
@@ -1702,9 +1701,9 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, hipStream_t st, const Ch
         em.em_med = adaptive ? c->med + 3 * s0 : nullptr; em.em_alpha = (float)alpha;
         if (usable) {
             CapParams p0 = cap_params(c, s, a.rmin, a.rmax);
-            if (stats_m2_applies(c, s, p0)) { em.em_m2 = 1; em.st_col0 = c->col0_pool + (size_t)s0 * 3 * s.PH; }
+            if (stats_m2_applies(c, s, p0)) { em.em_m2 = 1; em.st_col0 = stat_col0(c, s0); }
         } else if (c->stats_m2) {      // no capacity asked for: nobody reads the spectrum, the last forward step stores nothing
-            em.em_m2 = 2; em.st_col0 = c->col0_pool + (size_t)s0 * 3 * s.PH;
+            em.em_m2 = 2; em.st_col0 = stat_col0(c, s0);
         }
         // the stream bits in bucket order (the packed frames of the stream pipelines are expanded on the way).  (On the side stream
         // beside the forward transform it gained nothing measurable: 0.03 ms of 3.3.)
@@ -1758,7 +1757,7 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, hipStream_t st, const Ch
         } else {
             rc = enqueue_medians(c, s0, g, sst);
             if (rc) return rc;
-            HIPCHK(c, launch_capacity(c->spec(s0), p, g, c->med + 3 * s0, c->partial + (size_t)s0 * (3 * TFFT_STAT_MAX_BLOCKS + 1), usable, sst));
+            HIPCHK(c, launch_capacity(c->spec(s0), p, g, c->med + 3 * s0, stat_partial(c, s0), usable, sst, nullptr));
         }
     }
     if (delta) {
@@ -2659,12 +2658,6 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
     if ((stage == COLS_FWD_B || stage == COLS_INV_B) && pl.direct) launches = 0;
     if ((stage == COLS_FWD_A || stage == COLS_INV_B) && pl.fused_fwd) launches = 0;
     if (stage == ROWS_FWD && pl.fused_fwd && c->fuse_live && s.H < s.PH && (s.H % (s.PH >> 3)) != 0) launches = 2;      // one per live-row count
-    {
-        const bool compact = c->stats_compact && (unsigned long long)s.PH * s.PWi <= (1ull << 24);
-        const bool finish1 = compact && (unsigned long long)s.PH * s.PWi <= (1ull << 22) && n_images <= 4;
-        if (stage == MEDIANS) launches = compact ? (c->median_force_fallback ? 2 : (finish1 ? 5 : 7)) + (c->stats_fused ? 1 : 0)
-                                                 : (c->median_force_fallback ? 7 : 13) + (c->stats_fused ? 3 : 0);
-    }
     if (stage == CAPACITY) launches = c->stats_fused ? 0 : 2;      // fused: counted inside the medians' full pass
     // delta embedding (see embed_chunk): the batched pipeline has no k_embed launch, its first inverse step builds the tiles from the
     // bins and its row kernel adds the cover -- the stages are timed the way the pipeline runs them
@@ -2679,7 +2672,11 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
     // of the statistics -- sample pass + bracket guess before it, select chain, gated step, fallback and capacity kernels after it
     const bool tile = delta && bits_dev && tilestats_applies(c, s, pl, tcap, n_images) && (stage == final_fwd || stage == MEDIANS);
     const bool m2 = delta && bits_dev && !tile && stats_m2_applies(c, s, tcap);      // the spectrum is stored as |F|^2 + column 0 (see embed_chunk)
-    if (tile && stage == MEDIANS) launches = 10;
+    if (stage == MEDIANS) {
+        // tile: the sample pass and the gated plain step (FFT stages) + the statistics' own kernels around the COLS_STAT step
+        if (tile) launches = 2 + stat_tile_launches(stat_opts(c, &tcap, false));
+        else launches = plan_medians(s.PH, s.PWi, n_images, stat_opts(c, c->stats_fused ? &tcap : nullptr, m2)).launches;
+    }
 
     if (n_launches) *n_launches = launches;
     *ms_per_rep = 0.f;
@@ -2776,7 +2773,7 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
                 else rc = enqueue_medians(c, 0, n_images, c->stream);
                 break;
             case CAPACITY:
-                HIPCHK(c, launch_capacity(c->spec(0), tcap, n_images, c->med, c->partial, c->usable, c->stream));
+                HIPCHK(c, launch_capacity(c->spec(0), tcap, n_images, c->med, c->partial, c->usable, c->stream, nullptr));
                 break;
             default: rc = enqueue_fft_stage(c, 0, n_images, stage, (const uint8_t*)rgb_dev, (uint8_t*)rgb_out_dev, c->stream);
         }

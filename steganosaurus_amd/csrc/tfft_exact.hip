@@ -25,7 +25,7 @@ namespace tfft {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char tfft_smem[];
 
-// F[y][0] and F[y][M] out of the packed column 0 (as in tfft_kernels.hip)
+// F[y][0] and F[y][M] out of the packed column 0 (as unpack_col0 in tfft_device.h)
 __device__ __forceinline__ void exact_unpack_col0(const float2* __restrict__ plane, int y, int PH, int M, float2& f0, float2& fm) {
     const float2 a = plane[(size_t)y * M], b = plane[(size_t)((PH - y) & (PH - 1)) * M];
     f0 = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));

@@ -1,4 +1,5 @@
-// tfft_kernels.h -- parameter blocks and launchers shared by tfft_kernels.hip and tfft_capi.hip
+// tfft_kernels.h -- parameter blocks and launchers of tfft_kernels.hip, tfft_stats.hip, tfft_exact.hip and tfft_audit64.hip: the one
+// header tfft_capi.hip sees
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -43,7 +44,7 @@ struct ColParams {
     // em_fl (S:712-732 with a fixed alpha)
     float2* em_fl;                   // em_n values per image, indexed like rd_bins
     int em_m2;                       // COLS_EMIT: store |F|^2 (float, `out` reinterpreted, same byte offset per image) instead of the complex
-                                     // spectrum, the packed column 0 to st_col0: all the statistics read (launch_medians col0_m2)
+                                     // spectrum, the packed column 0 to st_col0: all the statistics read (launch_medians, StatOpts::m2)
     const uint8_t* em_pb;            // COLS_EMBED: em_n stream bits per image in the same order (k_gather_bits; 2 = not written)
     uint64_t em_n;                   // list stride between images (the length of the bin list; 0 with rd_walks, whose entry indices are absolute)
     float em_cos, em_sin;
@@ -220,12 +221,6 @@ hipError_t launch_fit_count(const TileBin* ent, const float2* fl, const uint8_t*
 hipError_t launch_fit_correct(const TileBin* ent, const float2* fl, const uint8_t* pb, const float2* jp, const float* mu, const unsigned* counts,
                               uint64_t n, int n_images, double gain, float2* d, hipStream_t s);
 // highest stored row any bin of the list touches -> *last_row (device int, reset here)
-hipError_t launch_stat_guess(const float2* mini, int PH, int PW, int Ms, size_t mini_img_stride, int n_images, SelectState* st, const struct CapParams* cap,
-                             unsigned* partial, int col0_packed, hipStream_t s);
-hipError_t launch_skew_bracket(SelectState* st, int n_images, int skew, hipStream_t s);
-hipError_t launch_stat_select(int PH, int n_images, SelectState* st, unsigned* cand, size_t cand_stride, float* med_out, const float2* col0, hipStream_t s);
-hipError_t launch_stat_settle(const float2* spec, int PH, int PW, size_t img_stride, int n_images, SelectState* st, float* med_out, const struct CapParams* cap,
-                              unsigned* partial, float* amb, unsigned long long* usable, hipStream_t s);
 hipError_t launch_gather_bits(const TileBin* ent, const unsigned* n_ent, const uint8_t* bits, const uint8_t* hdr, const uint8_t* pay, uint64_t plen,
                               uint64_t n, uint64_t limit, int n_images, uint8_t* out, hipStream_t s);
 // jitter (stream order) gathered into bucket order as unit phasors: out[e] = (cos, sin)(jitter[ent[e].bit]), e < *n_ent
@@ -235,15 +230,43 @@ hipError_t launch_embed(float2* spec, const tfft_bin* bins, const uint8_t* bits,
                         const EmbedParams& P, int n_images, int* err, hipStream_t s);
 hipError_t launch_read(const float2* spec, const tfft_bin* bins, const float* jitter, const EmbedParams& P,
                        int n_images, uint8_t* bits_out, int* err, hipStream_t s);
-// cap != nullptr: also S:998-1008 for every image (magmin in cap->magmin), counted inside the full median pass:
-// partial = [n_images*3*TFFT_STAT_MAX_BLOCKS] block counts, amb = [n_images*3*TFFT_AMB_CAP] parked |F|^2, usable[n_images]
-hipError_t launch_medians(const float2* spec, int PH, int PW, size_t img_stride, int n_images, SelectState* st,
-                          unsigned* cand, size_t cand_stride, float* med_out, int force_fallback, int fill_cus, int fill_resident, hipStream_t s,
-                          const CapParams* cap = nullptr, unsigned* partial = nullptr, float* amb = nullptr, unsigned long long* usable = nullptr,
-                          int compact = 1, const float2* col0_m2 = nullptr, int skew = 0);
+// ---- the statistics stage (tfft_stats.hip): medians of |F| per plane and, counted in the same pass, the capacities
+// the device buffers of the images of one launch (tfft_capi.hip: stat_bufs)
+struct StatBufs {
+    SelectState* st;                // 3 per image
+    unsigned* cand; size_t cand_stride;      // candidate lists, one per plane
+    float* med;                     // out: 3 medians per image
+    unsigned* partial;              // [n_images*3*TFFT_STAT_MAX_BLOCKS] block counts of the capacity + one flag per image
+    float* amb;                     // [n_images*3*TFFT_AMB_CAP] parked |F|^2
+    unsigned long long* usable;     // out: the capacities (with StatOpts::cap)
+    float2* col0;                   // [n_images*3*PH] packed columns 0 beside |F|^2 planes (StatOpts::m2) and of the COLS_STAT step
+};
+struct StatOpts {
+    const CapParams* cap;           // nullptr: medians only
+    bool m2;                        // the spectrum holds |F|^2 planes (ColParams::em_m2), the packed columns 0 are in StatBufs::col0
+    int compact;                    // 0: never the compact pipeline (TFFT_STATS_COMPACT)
+    int force_fallback;             // skip the fast path (TFFT_MEDIAN_FALLBACK)
+    int skew;                       // test hook (TFFT_STATS_SKEW): move the brackets so that the fast path fails
+    int fill_cus, fill_resident;    // CUs and resident k_collect_bracket blocks per CU (collect_bracket_resident_blocks); <= 0: 256, 4
+};
+// planes up to this many bins take the compact pipeline, and only those can be read as |F|^2 planes or settled inside the column step
+#define TFFT_COMPACT_MAX_BINS (1ull << 24)
+// ... and up to this many bins, in launches of so many images at most, its merged finish kernel
+#define TFFT_FINISH1_MAX_BINS (1ull << 22)
+#define TFFT_FINISH1_MAX_IMAGES 4
+struct MedianPlan { bool compact, finish1; int launches; };      // launches: kernels per launch_medians call
+MedianPlan plan_medians(int PH, int PW, int n_images, const StatOpts& o);
+hipError_t launch_medians(const float2* spec, int PH, int PW, size_t img_stride, int n_images, const StatBufs& b, const StatOpts& o, hipStream_t s);
+// the statistics around a COLS_STAT step: bracket guess before it, select and settle after it; stat_tile_launches: their kernels
+hipError_t launch_stat_guess(const float2* mini, int PH, int PW, int Ms, size_t mini_img_stride, int col0_packed, int n_images, const StatBufs& b,
+                             const StatOpts& o, hipStream_t s);
+hipError_t launch_stat_select(int PH, int n_images, const StatBufs& b, hipStream_t s);
+hipError_t launch_stat_settle(const float2* spec, int PH, int PW, size_t img_stride, int n_images, const StatBufs& b, const StatOpts& o, hipStream_t s);
+int stat_tile_launches(const StatOpts& o);
 int collect_bracket_resident_blocks();
+// only_flagged: nullptr, or one word per image -- images whose word is 0 are skipped
 hipError_t launch_capacity(const float2* spec, const CapParams& P, int n_images, const float* med_dev,
-                           unsigned* partial, unsigned long long* usable, hipStream_t s, const unsigned* only_flagged = nullptr);
+                           unsigned* partial, unsigned long long* usable, hipStream_t s, const unsigned* only_flagged);
 hipError_t launch_frame_expand(const uint8_t* header, const uint8_t* payload, uint64_t plen, int n_images, uint8_t* bits,
                                uint64_t stride, hipStream_t s);      // image i's bits at bits + i*stride
 hipError_t launch_frame_majority(const uint8_t* bits, uint64_t plen, int n_images, uint8_t* header, uint8_t* payload,

@@ -116,9 +116,27 @@ def check_forward_golden(lib, golden_dir, wh, center):
     ctx.close()
 
 
-def check_median_paths(lib, orc, sizes):
+# TFFT_STATS_COMPACT=0: the statistics' pipeline of separate launches -- k_select_init, k_select<1..3>, k_collect, the plain level-3
+# histogram, k_capacity for the flagged images -- which planes above 2^24 bins always take, at any size
+PLAIN_PIPELINE = {"TFFT_STATS_COMPACT": "0"}
+PLAIN_PIPELINE_ENVS = (PLAIN_PIPELINE, dict(PLAIN_PIPELINE, TFFT_MEDIAN_FALLBACK="1"), dict(PLAIN_PIPELINE, TFFT_STATS_FUSED="0"),
+                       dict(PLAIN_PIPELINE, TFFT_STATS_SKEW="5"))
+
+
+def check_median_paths(lib, orc, sizes, env=None):
     """The sampled fast path and the forced full fallback give the same exact order statistic; on
-    ordinary covers the fast path is the one that runs."""
+    ordinary covers the fast path is the one that runs.  env: set around the whole check."""
+    if env:
+        old = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        try:
+            return check_median_paths(lib, orc, sizes)
+        finally:
+            for k, v in old.items():
+                if v is None:
+                    del os.environ[k]
+                else:
+                    os.environ[k] = v
     for (w, h) in sizes:
         img = cover_rgb(w, h, 4)
         _, want = orc.forward_rgb8(img, want_spec=False)

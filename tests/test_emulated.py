@@ -49,6 +49,10 @@ def test_median_fast_and_fallback_paths(emu, orc):
     PC.check_median_paths(emu, orc, [(64, 64), (48, 40), (8, 4), (128, 32)])
 
 
+def test_median_paths_of_the_plain_pipeline(emu, orc):
+    PC.check_median_paths(emu, orc, [(64, 64), (48, 40), (8, 4), (128, 32)], env=PC.PLAIN_PIPELINE)
+
+
 def test_fused_rows_plus_column_step(emu, orc):
     # PW = 2048 and PH >= 128: k_rowcol_fwd (rows + length-8 column step in one kernel), then step B
     PC.check_forward_against_oracle(emu, orc, [(1500, 130), (2047, 129)], centers=(0, 1))
@@ -381,3 +385,8 @@ def test_batch_capacity_inside_the_median_pass(emu):
     PC.check_batch_capacity(emu, PC.HostBufs, 40, 200, nimg=1, cases=((0.0, 1.5, 0.5),), envs=small)
     # fused 2048-wide plan: the statistics inside the last forward column step (COLS_STAT); a flat image among them
     PC.check_batch_capacity(emu, PC.HostBufs, 2040, 130, nimg=2, cases=((0.05, 0.45, 0.01), (0.05, 0.45, 1.0)), flat=True, envs=({"TFFT_STATS_TILE": "2"},))
+
+
+def test_batch_capacity_of_the_plain_pipeline(emu):
+    PC.check_batch_capacity(emu, PC.HostBufs, 96, 64, nimg=2, envs=PC.PLAIN_PIPELINE_ENVS)
+    PC.check_batch_capacity(emu, PC.HostBufs, 40, 200, nimg=1, cases=((0.0, 1.5, 0.5),), envs=PC.PLAIN_PIPELINE_ENVS)

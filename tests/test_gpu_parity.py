@@ -83,6 +83,10 @@ def test_median_fast_and_fallback_paths(lib, orc):
     PC.check_median_paths(lib, orc, [(64, 64), (48, 40), (8, 4), (512, 512), (1920, 1080)])
 
 
+def test_median_paths_of_the_plain_pipeline(lib, orc):
+    PC.check_median_paths(lib, orc, [(64, 64), (48, 40), (8, 4), (128, 32)], env=PC.PLAIN_PIPELINE)
+
+
 def test_identity_roundtrip(lib):
     PC.check_identity_roundtrip(lib, [(64, 64), (48, 40), (33, 17), (2, 2), (1, 1), (5, 1), (1, 7), (12, 1024),
                                       (512, 512), (1920, 1080), (3840, 2160)])
@@ -605,6 +609,11 @@ def test_batch_capacity_inside_the_median_pass(lib):
     # and of 25 M bins a couple sit within fp32 rounding of their own median)
     PC.check_batch_capacity(lib, PC.TorchBufs, 3840, 2160, nimg=2, cases=((0.05, 0.45, 0.01), (0.1, 0.6, 0.3)))
     PC.check_batch_capacity(lib, PC.TorchBufs, 100, 2000, nimg=2, cases=((0.05, 0.45, 0.01), (0.0, 1.5, 0.5)))
+
+
+def test_batch_capacity_of_the_plain_pipeline(lib):
+    PC.check_batch_capacity(lib, PC.TorchBufs, 96, 64, nimg=2, envs=PC.PLAIN_PIPELINE_ENVS)
+    PC.check_batch_capacity(lib, PC.TorchBufs, 40, 200, nimg=1, cases=((0.0, 1.5, 0.5),), envs=PC.PLAIN_PIPELINE_ENVS)
 
 
 def test_graph_replay_matches_plain_launches(lib, orc):

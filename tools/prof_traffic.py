@@ -54,7 +54,8 @@ for stage, pat in {
     if b is not None:
         stages[stage] = int(b * 1024)
         kernels[stage] = name
-med = [kib(k) for k in S if k.startswith("k_collect_bracket")] + [kib(k) or 0 for k in ("k_hist_spec", "k_hist_cand<true>", "k_hist_cand2", "k_col0_stats")]
+# (k_hist_cand<1> / <0>: CAND_FAST3 / CAND_LEVEL2 of tfft_stats.hip)
+med = [kib(k) for k in S if k.startswith("k_collect_bracket")] + [kib(k) or 0 for k in ("k_hist_spec", "k_hist_cand<1>", "k_hist_cand<0>", "k_col0_stats")]
 if any(re.match(r"k_fft_cols<\d+, 1, 5, ", k) for k in S):      # statistics inside the last forward step: their sample pass is the plain last step over every 8th tile
     med += [kib(k) or 0 for k in S if re.match(r"k_fft_cols<\d+, 1, 0, (true|false), false, true>", k)]
 med = [m for m in med if m is not None]
