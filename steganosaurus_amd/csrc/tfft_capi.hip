@@ -258,33 +258,71 @@ int regrow(tfft_ctx* c, std::initializer_list<Regrow> bufs) {
     return TFFT_OK;
 }
 
-static void copy_embed_fields(ColParams& cp, const ColParams& e, bool inverse) {
-    cp.rd_bins = e.rd_bins; cp.rd_off = e.rd_off; cp.trash = e.trash; cp.rd_walks = e.rd_walks;
-    cp.em_n = e.em_n; cp.em_cos = e.em_cos; cp.em_sin = e.em_sin; cp.em_fl = e.em_fl; cp.em_pb = e.em_pb; cp.em_on = 1; cp.em_m2 = e.em_m2;
-    if (inverse) { cp.em_jp = e.em_jp; cp.em_med = e.em_med; cp.em_alpha = e.em_alpha; cp.em_dsrc = e.em_dsrc; }      // (the phase options belong to COLS_EMBED)
-    cp.st_sel = e.st_sel; cp.st_cand = e.st_cand; cp.st_cand_stride = e.st_cand_stride; cp.st_partial = e.st_partial; cp.st_amb = e.st_amb;
-    cp.st_col0 = e.st_col0; cp.st_slo = e.st_slo; cp.st_shi = e.st_shi; cp.st_cap = e.st_cap; cp.st_PW = e.st_PW;
-}
-
-static void copy_plain_extra(ColParams& cp, const ColParams& e) {
-    if (e.tile_step > 1) cp.tiles_per_block = e.hist_sel ? 2 : 1;      // the sample: an eighth of the tiles; few per workgroup keep the grid wide
-    cp.tile_step = e.tile_step; cp.tile_off = e.tile_off; cp.out_M = e.out_M; cp.out_plane_stride = e.out_plane_stride; cp.out_img_stride = e.out_img_stride; cp.gate = e.gate;
-    cp.hist_sel = e.hist_sel; cp.g_step = e.g_step; cp.g_off = e.g_off;
-}
-
 // How a launch sequence wants the outer column steps and the inverse row kernel to run: handed down explicitly per call (until round 3
 // these were pointers parked in the context around a call -- to stack objects, and left dangling by any early return in between).
+// A step's parameter object carries the fields its mode reads (tfft_kernels.h: ColParams says which); the geometry, the DC tables, the
+// scratch line and tiles_per_block are the stage's own (last_forward_params, first_inverse_params)
 struct StageMode {
-    const ColParams* fwd_emit = nullptr;   // the last forward column step also writes the values of the listed bins (COLS_EMIT, delta embedding)
-    const ColParams* fwd_read = nullptr;   // the last forward column step runs in COLS_READ mode with these rd_* fields (no spectrum stored)
-    const int* fwd_last_row = nullptr;     // the last forward column step stores rows <= *fwd_last_row only (COLS_ROWLIMIT)
-    const ColParams* inv_embed = nullptr;  // the first inverse column step runs in COLS_EMBED mode (delta embedding) with these rd_*/em_* fields
-    const uint8_t* inv_cover = nullptr;    // ... and the inverse row kernel adds its transform to these cover pixels
-    const ColParams* fwd_plain_extra = nullptr;   // plain last forward step: tile_step / out_* (the statistics' sample) or gate fields, and ...
-    float2* fwd_out_override = nullptr;           // ... its output buffer
+    int fwd_mode = COLS_PLAIN;             // the last forward column step: COLS_PLAIN (fwd: the statistics' sample or the gate, or nullptr),
+    const ColParams* fwd = nullptr;        // COLS_ROWLIMIT, COLS_READ, COLS_EMIT or COLS_STAT
+    float2* fwd_out_override = nullptr;    // ... and its output buffer
+    int inv_mode = COLS_PLAIN;             // the first inverse column step: COLS_PLAIN (inv: nullptr), COLS_EMBED or COLS_EMBED_D (delta embedding)
+    const ColParams* inv = nullptr;
+    bool walks = false;                    // the lists are one walk per image (ColStep::walks).  One flag for both steps: a caller fills
+                                           // in the step its launch sequence runs in a bucket mode, and the flag goes with that step (a COLS_PLAIN
+                                           // or COLS_ROWLIMIT step has no lists: launch_cols rejects it with the flag set)
+    const uint8_t* inv_cover = nullptr;    // the inverse row kernel adds its transform to these cover pixels (delta embedding)
     bool inv_via_spec = false;             // delta embedding: the inverse keeps its intermediate in `spec` (nothing reads F there), so `tmp` -- the
                                            // input of the last forward step -- survives for the gated fallback of the in-kernel statistics
 };
+
+// a column step's parameters: the fields of `from` (or none) + what every step of slot geometry s shares
+static ColParams col_params(const tfft_ctx* c, const Slot& s, const ColParams* from) {
+    ColParams cp = from ? *from : ColParams{};
+    cp.M = s.PWi / 2; cp.PH = s.PH; cp.plane_stride = (size_t)s.PH * cp.M; cp.img_stride = c->slot_stride;
+    cp.tiles_per_block = c->cols_tiles_per_block;
+    return cp;
+}
+static int dc_tables(tfft_ctx* c, const Slot& s, ColParams& cp) {
+    if (c->dc_bias == 0.0f) return TFFT_OK;
+    int rc = get_dc_table(c, s.H, s.PH, s.center, 0, (double)c->dc_bias, &cp.dc_ah);
+    if (!rc) rc = get_dc_table(c, s.W, s.PWi, s.center, 1, 1.0, &cp.dc_aw);
+    return rc;
+}
+// the last forward column step: the only one of a direct plan, else for every k1 the length-N2 FFT over rows k1*N2+n2 -> rows k1+N1*k2
+static int last_forward_params(tfft_ctx* c, const Slot& s, const ColPlan& pl, const StageMode& md, ColParams& cp) {
+    const int N1 = 1 << pl.log_n1, N2 = 1 << pl.log_n2;
+    cp = col_params(c, s, md.fwd);
+    if (pl.direct) { cp.G = 1; cp.in_a = 1; cp.in_b = 0; cp.out_a = 1; cp.out_b = 0; cp.in_rows = s.H; }
+    else { cp.G = N1; cp.in_a = 1; cp.in_b = N2; cp.out_a = N1; cp.out_b = 1; cp.in_rows = s.PH; }
+    cp.out_rows = s.PH; cp.tw_out = 0;
+    switch (md.fwd_mode) {
+        case COLS_PLAIN:
+            if (cp.tile_step > 1) cp.tiles_per_block = cp.hist_sel ? 2 : 1;      // the sample: an eighth of the tiles; few per workgroup keep the grid wide
+            break;
+        case COLS_READ: cp.trash = c->trash; cp.tiles_per_block = c->cols_tiles_read; break;
+        case COLS_EMIT: case COLS_STAT:
+            cp.trash = c->trash;
+            cp.em_jp = nullptr; cp.em_med = nullptr; cp.em_alpha = 0.f;      // (the phase options belong to COLS_EMBED, whose object this may be)
+            if (!c->cols_tiles_forced && pl.log_n2 <= 8) cp.tiles_per_block = 2;
+            if (md.fwd_mode == COLS_STAT && c->cols_tiles_stat) cp.tiles_per_block = c->cols_tiles_stat;
+            break;
+    }
+    return dc_tables(c, s, cp);
+}
+// the first inverse column step: the only one of a direct plan, else for every k1 the length-N2 inverse over rows k1+N1*k2 -> rows
+// k1*N2+n2, times w^-(n2*k1)
+static int first_inverse_params(tfft_ctx* c, const Slot& s, const ColPlan& pl, const StageMode& md, ColParams& cp) {
+    const int N1 = 1 << pl.log_n1, N2 = 1 << pl.log_n2;
+    cp = col_params(c, s, md.inv);
+    if (pl.direct) { cp.G = 1; cp.in_a = 1; cp.in_b = 0; cp.out_a = 1; cp.out_b = 0; cp.out_rows = s.H; cp.tw_out = 0; }
+    else { cp.G = N1; cp.in_a = N1; cp.in_b = 1; cp.out_a = 1; cp.out_b = N2; cp.out_rows = s.PH; cp.tw_out = 1; }
+    cp.in_rows = s.PH;
+    if (!embed_mode(md.inv_mode)) return dc_tables(c, s, cp);      // (the tiles of a delta embed hold F' - F: no DC term to take out)
+    cp.trash = c->trash;
+    cp.tiles_per_block = c->cols_tiles_embed ? c->cols_tiles_embed : (pl.log_n2 >= 9 ? 2 : 16);
+    return TFFT_OK;
+}
 
 int enqueue_fft_stage(tfft_ctx* c, int s0, int n, int stage, const uint8_t* rgb_in, uint8_t* rgb_out, hipStream_t st, const StageMode& md = StageMode()) {
     const Slot& s = c->slots[s0];
@@ -293,11 +331,15 @@ int enqueue_fft_stage(tfft_ctx* c, int s0, int n, int stage, const uint8_t* rgb_
     int rc = get_twiddles(c, s.PWi, &tw_w); if (rc) return rc;
     rc = get_twiddles(c, s.PH, &tw_h); if (rc) return rc;
     const ColPlan pl = plan_cols(c, s.PH, s.PWi, n);
-    const int N1 = 1 << pl.log_n1, N2 = 1 << pl.log_n2;
+    const int N2 = 1 << pl.log_n2;
     float2 *spec = c->spec(s0), *tmp = c->tmp(s0);
-    ColParams cp{};
-    cp.M = M; cp.PH = s.PH; cp.plane_stride = (size_t)s.PH * M; cp.img_stride = c->slot_stride;
-    cp.tiles_per_block = c->cols_tiles_per_block;
+    float2* inv_mid = md.inv_via_spec ? spec : tmp;      // where the inverse keeps its intermediate
+    ColParams cp = col_params(c, s, nullptr);
+    auto last_forward = [&]() -> int {
+        rc = last_forward_params(c, s, pl, md, cp); if (rc) return rc;
+        HIPCHK(c, launch_cols(tmp, md.fwd_out_override ? md.fwd_out_override : spec, tw_h, cp, ColStep{pl.log_n2, +1, md.fwd_mode, md.walks}, 3 * n, st));
+        return TFFT_OK;
+    };
     switch (stage) {
         case ROWS_FWD: {
             RowParams rp{s.W, s.H, s.PWi, s.PH, s.center, 0.f, c->slot_stride, c->dc_bias, nullptr};
@@ -309,67 +351,29 @@ int enqueue_fft_stage(tfft_ctx* c, int s0, int n, int stage, const uint8_t* rgb_
         }
         case COLS_FWD_A:
             if (pl.fused_fwd) return TFFT_OK;       // done inside ROWS_FWD
-            if (pl.direct) {
-                cp.G = 1; cp.in_a = 1; cp.in_b = 0; cp.out_a = 1; cp.out_b = 0; cp.in_rows = s.H; cp.out_rows = s.PH; cp.tw_out = 0;
-                cp.last_row_dev = md.fwd_last_row;
-            if (c->dc_bias != 0.0f) {
-                rc = get_dc_table(c, s.H, s.PH, s.center, 0, (double)c->dc_bias, &cp.dc_ah); if (rc) return rc;
-                rc = get_dc_table(c, s.W, s.PWi, s.center, 1, 1.0, &cp.dc_aw); if (rc) return rc;
-            }
-                if (md.fwd_read) { const ColParams& r = *md.fwd_read; cp.rd_bins = r.rd_bins; cp.rd_off = r.rd_off; cp.rd_bits = r.rd_bits; cp.rd_n = r.rd_n; cp.em_jp = r.em_jp; cp.rd_walks = r.rd_walks; cp.trash = c->trash; cp.tiles_per_block = c->cols_tiles_read; }
-                else if (md.fwd_emit) { copy_embed_fields(cp, *md.fwd_emit, false); if (!c->cols_tiles_forced && pl.log_n2 <= 8) cp.tiles_per_block = 2; if (cp.st_sel && c->cols_tiles_stat) cp.tiles_per_block = c->cols_tiles_stat; }
-                else if (md.fwd_plain_extra) copy_plain_extra(cp, *md.fwd_plain_extra);
-                HIPCHK(c, launch_cols(tmp, md.fwd_out_override ? md.fwd_out_override : spec, tw_h, cp, pl.log_n2, +1, 3 * n, st));
-            } else {   // for every n2: length-N1 FFT over rows n1*N2+n2, times w^(n2*k1), in place
-                cp.G = N2; cp.in_a = N2; cp.in_b = 1; cp.out_a = N2; cp.out_b = 1; cp.in_rows = s.H; cp.out_rows = s.PH; cp.tw_out = 1;
-                HIPCHK(c, launch_cols(tmp, tmp, tw_h, cp, pl.log_n1, +1, 3 * n, st));
-            }
+            if (pl.direct) return last_forward();
+            // for every n2: length-N1 FFT over rows n1*N2+n2, times w^(n2*k1), in place
+            cp.G = N2; cp.in_a = N2; cp.in_b = 1; cp.out_a = N2; cp.out_b = 1; cp.in_rows = s.H; cp.out_rows = s.PH; cp.tw_out = 1;
+            HIPCHK(c, launch_cols(tmp, tmp, tw_h, cp, ColStep{pl.log_n1, +1, COLS_PLAIN, false}, 3 * n, st));
             return TFFT_OK;
         case COLS_FWD_B:
-            if (pl.direct) return TFFT_OK;
-            // for every k1: length-N2 FFT over rows k1*N2+n2 -> rows k1+N1*k2
-            cp.G = N1; cp.in_a = 1; cp.in_b = N2; cp.out_a = N1; cp.out_b = 1; cp.in_rows = s.PH; cp.out_rows = s.PH; cp.tw_out = 0;
-            cp.last_row_dev = md.fwd_last_row;
-            if (c->dc_bias != 0.0f) {
-                rc = get_dc_table(c, s.H, s.PH, s.center, 0, (double)c->dc_bias, &cp.dc_ah); if (rc) return rc;
-                rc = get_dc_table(c, s.W, s.PWi, s.center, 1, 1.0, &cp.dc_aw); if (rc) return rc;
-            }
-            if (md.fwd_read) { const ColParams& r = *md.fwd_read; cp.rd_bins = r.rd_bins; cp.rd_off = r.rd_off; cp.rd_bits = r.rd_bits; cp.rd_n = r.rd_n; cp.em_jp = r.em_jp; cp.rd_walks = r.rd_walks; cp.trash = c->trash; cp.tiles_per_block = c->cols_tiles_read; }
-            else if (md.fwd_emit) { copy_embed_fields(cp, *md.fwd_emit, false); if (!c->cols_tiles_forced && pl.log_n2 <= 8) cp.tiles_per_block = 2; if (cp.st_sel && c->cols_tiles_stat) cp.tiles_per_block = c->cols_tiles_stat; }
-                else if (md.fwd_plain_extra) copy_plain_extra(cp, *md.fwd_plain_extra);
-            HIPCHK(c, launch_cols(tmp, md.fwd_out_override ? md.fwd_out_override : spec, tw_h, cp, pl.log_n2, +1, 3 * n, st));
-            return TFFT_OK;
+            return pl.direct ? TFFT_OK : last_forward();
         case COLS_INV_A:
-            if (pl.direct) {
-                cp.G = 1; cp.in_a = 1; cp.in_b = 0; cp.out_a = 1; cp.out_b = 0; cp.in_rows = s.PH; cp.out_rows = s.H; cp.tw_out = 0;
-                if (md.inv_embed) { copy_embed_fields(cp, *md.inv_embed, true); cp.tiles_per_block = c->cols_tiles_embed ? c->cols_tiles_embed : (pl.log_n2 >= 9 ? 2 : 16); }
-                else if (c->dc_bias != 0.0f) {
-                    rc = get_dc_table(c, s.H, s.PH, s.center, 0, (double)c->dc_bias, &cp.dc_ah); if (rc) return rc;
-                    rc = get_dc_table(c, s.W, s.PWi, s.center, 1, 1.0, &cp.dc_aw); if (rc) return rc;
-                }
-                HIPCHK(c, launch_cols(spec, md.inv_via_spec ? spec : tmp, tw_h, cp, pl.log_n2, -1, 3 * n, st));
-            } else {   // for every k1: length-N2 inverse over rows k1+N1*k2 -> rows k1*N2+n2, times w^-(n2*k1)
-                cp.G = N1; cp.in_a = N1; cp.in_b = 1; cp.out_a = 1; cp.out_b = N2; cp.in_rows = s.PH; cp.out_rows = s.PH; cp.tw_out = 1;
-                if (md.inv_embed) { copy_embed_fields(cp, *md.inv_embed, true); cp.tiles_per_block = c->cols_tiles_embed ? c->cols_tiles_embed : (pl.log_n2 >= 9 ? 2 : 16); }
-                else if (c->dc_bias != 0.0f) {
-                    rc = get_dc_table(c, s.H, s.PH, s.center, 0, (double)c->dc_bias, &cp.dc_ah); if (rc) return rc;
-                    rc = get_dc_table(c, s.W, s.PWi, s.center, 1, 1.0, &cp.dc_aw); if (rc) return rc;
-                }
-                HIPCHK(c, launch_cols(spec, md.inv_via_spec ? spec : tmp, tw_h, cp, pl.log_n2, -1, 3 * n, st));
-            }
+            rc = first_inverse_params(c, s, pl, md, cp); if (rc) return rc;
+            HIPCHK(c, launch_cols(spec, inv_mid, tw_h, cp, ColStep{pl.log_n2, -1, md.inv_mode, md.walks}, 3 * n, st));
             return TFFT_OK;
         case COLS_INV_B:
             if (pl.direct || pl.fused_fwd) return TFFT_OK;      // fused: done inside ROWS_INV
             // for every n2: length-N1 inverse over rows k1*N2+n2 -> rows n1*N2+n2 (< H only), in place
             cp.G = N2; cp.in_a = N2; cp.in_b = 1; cp.out_a = N2; cp.out_b = 1; cp.in_rows = s.PH; cp.out_rows = s.H; cp.tw_out = 0;
-            HIPCHK(c, launch_cols(md.inv_via_spec ? spec : tmp, md.inv_via_spec ? spec : tmp, tw_h, cp, pl.log_n1, -1, 3 * n, st));
+            HIPCHK(c, launch_cols(inv_mid, inv_mid, tw_h, cp, ColStep{pl.log_n1, -1, COLS_PLAIN, false}, 3 * n, st));
             return TFFT_OK;
         case ROWS_INV: {
             RowParams rp{s.W, s.H, s.PWi, s.PH, s.center, (float)(1.0 / ((double)M * (double)s.PH)), c->slot_stride, c->dc_bias, nullptr};
             if (md.inv_cover) { rp.cover = md.inv_cover; rp.bias = 0.f; }      // delta embedding: the transform of F' - F has no DC term to give back
-            if (md.inv_via_spec && !md.inv_embed) return TFFT_E_INVALID;      // only the delta inverse reads nothing from `spec`
-            if (pl.fused_fwd) HIPCHK(c, launch_colrow_inv(md.inv_via_spec ? spec : tmp, rgb_out, tw_w, rp, n, st));       // column step B' + rows
-            else HIPCHK(c, launch_rows_inv(md.inv_via_spec ? spec : tmp, rgb_out, tw_w, rp, n, st));
+            if (md.inv_via_spec && !embed_mode(md.inv_mode)) return TFFT_E_INVALID;      // only the delta inverse reads nothing from `spec`
+            if (pl.fused_fwd) HIPCHK(c, launch_colrow_inv(inv_mid, rgb_out, tw_w, rp, n, st));       // column step B' + rows
+            else HIPCHK(c, launch_rows_inv(inv_mid, rgb_out, tw_w, rp, n, st));
             return TFFT_OK;
         }
         default: return TFFT_E_INVALID;
@@ -1433,10 +1437,10 @@ static BucketGeom bucket_geom(const tfft_ctx* c, const Slot& s, int g) {
     const int G = pl.direct ? 1 : (1 << pl.log_n1), ntiles = (s.PWi / 2 + 15) / 16;
     return BucketGeom{G, ntiles, 3 * ntiles * G};
 }
-// the head of a bucketed ColParams: the entries and offsets built on compute stream `which`, and where lanes without an entry store
+// the head of a bucketed ColParams: the entries and offsets built on compute stream `which`
 static ColParams bucketed_params(const tfft_ctx* c, int which) {
     ColParams cp{};
-    cp.rd_bins = c->tb[which].ent; cp.rd_off = c->tb[which].off; cp.trash = c->trash;
+    cp.rd_bins = c->tb[which].ent; cp.rd_off = c->tb[which].off;
     return cp;
 }
 
@@ -1575,7 +1579,7 @@ static int enqueue_tilestats_tail(tfft_ctx* c, int s0, int g, const uint8_t* rgb
     const ColPlan pl = plan_cols(c, s.PH, s.PWi, g);
     ColParams gt{};
     gt.gate = c->sel + 3 * s0;
-    StageMode mg; mg.fwd_plain_extra = &gt;
+    StageMode mg; mg.fwd_mode = COLS_PLAIN; mg.fwd = &gt;
     int rc = enqueue_fft_stage(c, s0, g, pl.direct ? COLS_FWD_A : COLS_FWD_B, rgb_in, nullptr, st, mg);
     if (rc) return rc;
     HIPCHK(c, launch_stat_settle(c->spec(s0), s.PH, s.PWi, c->slot_stride, g, stat_bufs(c, s0, usable), stat_opts(c, &cap, false), st));
@@ -1585,8 +1589,8 @@ static int enqueue_tilestats_tail(tfft_ctx* c, int s0, int g, const uint8_t* rgb
 
 // phases (tfft_profile_stage times them apart): 1 the steps before the last column step, 2 sample + bracket guess, 4 the COLS_STAT step,
 // 8 select, 16 gated spectrum + fallbacks + capacity
-static int enqueue_forward_tilestats(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, hipStream_t st, ColParams& em, const CapParams& cap,
-                                     unsigned long long* usable, int phases = 31) {
+static int enqueue_forward_tilestats(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, hipStream_t st, const ColParams& em, bool walks,
+                                     const CapParams& cap, unsigned long long* usable, int phases = 31) {
     const Slot& s = c->slots[s0];
     const ColPlan pl = plan_cols(c, s.PH, s.PWi, g);
     const int final_fwd = pl.direct ? COLS_FWD_A : COLS_FWD_B;
@@ -1619,20 +1623,20 @@ static int enqueue_forward_tilestats(tfft_ctx* c, int s0, int g, const uint8_t* 
     ex.hist_sel = sb.st; ex.g_step = g_step; ex.g_off = g_step / 2;
     if (phases & 2) {
         StageMode ms;
-        ms.fwd_plain_extra = &ex;
+        ms.fwd_mode = COLS_PLAIN; ms.fwd = &ex;
         rc = enqueue_fft_stage(c, s0, g, final_fwd, rgb_in, nullptr, st, ms);
         if (rc) return rc;
         HIPCHK(c, launch_stat_guess(nullptr, s.PH, s.PWi, Ms, ex.out_img_stride, 0, g, sb, stat_opts(c, &cap, false), st));
     }
     // (2) the last forward step: values of the listed bins + the bracket pass on every value
     if (phases & 4) {
-    em.st_sel = sb.st; em.st_cand = sb.cand; em.st_cand_stride = sb.cand_stride; em.st_partial = sb.partial; em.st_amb = sb.amb; em.st_col0 = sb.col0;
-    em.st_slo = cap.s_lo > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)cap.s_lo; em.st_shi = cap.s_hi > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)cap.s_hi;
-    em.st_cap = 1; em.st_PW = cap.PW;
-    { StageMode me; me.fwd_emit = &em;
-      rc = enqueue_fft_stage(c, s0, g, final_fwd, rgb_in, nullptr, st, me); }
-    em.st_sel = nullptr;
-    if (rc) return rc;
+        ColParams sp = em;
+        sp.st_sel = sb.st; sp.st_cand = sb.cand; sp.st_cand_stride = sb.cand_stride; sp.st_partial = sb.partial; sp.st_amb = sb.amb; sp.st_col0 = sb.col0;
+        sp.st_slo = cap.s_lo > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)cap.s_lo; sp.st_shi = cap.s_hi > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)cap.s_hi;
+        sp.st_cap = 1; sp.st_PW = cap.PW;
+        StageMode me; me.fwd_mode = COLS_STAT; me.fwd = &sp; me.walks = walks;
+        rc = enqueue_fft_stage(c, s0, g, final_fwd, rgb_in, nullptr, st, me);
+        if (rc) return rc;
     }
     if (phases & 8) {
         rc = enqueue_tilestats_select(c, s0, g, st);
@@ -1694,7 +1698,7 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, hipStream_t st, const Ch
         auto& tb = c->tb[which];
         em = bucketed_params(c, which);
         em.em_fl = tb.fl + (size_t)s0 * n_bits; em.em_pb = tb.pb + (size_t)s0 * n_bits;
-        em.em_n = walks ? 0 : n_bits; em.em_cos = ep.cos_a; em.em_sin = ep.sin_a; em.rd_walks = walks ? 1 : 0;      // (walks: entry indices are absolute)
+        em.em_n = walks ? 0 : n_bits; em.em_cos = ep.cos_a; em.em_sin = ep.sin_a;      // (walks: entry indices are absolute)
         if (!walks) rc = gather_jitter(c, which, n_bits, nb, st);
         if (rc) return rc;
         em.em_jp = jit ? tb.jp : nullptr;
@@ -1717,7 +1721,7 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, hipStream_t st, const Ch
         p.magmin = a.magmin;
         if (tilestats_applies(c, s, plan_cols(c, s.PH, s.PWi, g), p, g)) {
             em.em_m2 = 0;
-            rc = enqueue_forward_tilestats(c, s0, g, rgb_in, st, em, p, usable, 7);
+            rc = enqueue_forward_tilestats(c, s0, g, rgb_in, st, em, walks, p, usable, 7);
             if (rc) return rc;
             // the select chain is five small dependent launches: on a side stream beside the inverse transform, which does not wait for it
             hipStream_t sst = st;
@@ -1730,7 +1734,7 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, hipStream_t st, const Ch
                 if (rc) return rc;
             }
             StageMode mi;
-            mi.inv_embed = &em; mi.inv_cover = rgb_in; mi.inv_via_spec = true;
+            mi.inv_mode = COLS_EMBED; mi.inv = &em; mi.walks = walks; mi.inv_cover = rgb_in; mi.inv_via_spec = true;
             rc = enqueue_inverse(c, s0, g, rgb_out, st, mi);
             if (rc) return rc;
             if (sst != st) {
@@ -1741,7 +1745,7 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, hipStream_t st, const Ch
         }
     }
     StageMode md;
-    if (delta) md.fwd_emit = &em;
+    if (delta) { md.fwd_mode = COLS_EMIT; md.fwd = &em; md.walks = walks; }
     rc = enqueue_forward(c, s0, g, rgb_in, st, md);
     if (rc) return rc;
     hipStream_t sst = st;       // the stream the statistics run on
@@ -1762,7 +1766,7 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, hipStream_t st, const Ch
     }
     if (delta) {
         StageMode mi;
-        mi.inv_embed = &em; mi.inv_cover = rgb_in;
+        mi.inv_mode = COLS_EMBED; mi.inv = &em; mi.walks = walks; mi.inv_cover = rgb_in;
         rc = enqueue_inverse(c, s0, g, rgb_out, st, mi);
         if (async) {            // whoever waits for the context's stream has the capacities too
             const int rj = stats_join(c, which, st);
@@ -1828,9 +1832,9 @@ static int extract_chunk(tfft_ctx* c, int s0, int g, hipStream_t st, const Chunk
         if (rc) return rc;
         ColParams rd = bucketed_params(c, which);
         rd.rd_bits = bits_out; rd.rd_n = n_bits;
-        rd.em_jp = jit ? tb.jp : nullptr; rd.rd_walks = walks ? 1 : 0;
+        rd.em_jp = jit ? tb.jp : nullptr;
         StageMode md;
-        md.fwd_read = &rd;
+        md.fwd_mode = COLS_READ; md.fwd = &rd; md.walks = walks;
         rc = enqueue_forward(c, s0, g, rgb_in, st, md);
         if (rc) return rc;
     } else {
@@ -1843,8 +1847,10 @@ static int extract_chunk(tfft_ctx* c, int s0, int g, hipStream_t st, const Chunk
             HIPCHK(c, launch_bins_last_row(bins, walks ? (uint64_t)g * n_bits : n_bits, s.PH, s.PWi, last_row, st));
             tbr.row_for = registered ? bins : nullptr; tbr.row_n = n_bits; tbr.row_ph = s.PH; tbr.row_pw = s.PWi;
         }
+        ColParams rl{};
+        rl.last_row_dev = last_row;
         StageMode md;
-        md.fwd_last_row = last_row;
+        md.fwd_mode = COLS_ROWLIMIT; md.fwd = &rl;
         rc = enqueue_forward(c, s0, g, rgb_in, st, md);
         if (rc) return rc;
         HIPCHK(c, launch_read(c->spec(s0), bins, jit, ep, g, bits_out, c->err, st));
@@ -2298,9 +2304,9 @@ static int ensure_fit(tfft_ctx* c, uint64_t n_bins) {
 static int fit_forward(tfft_ctx* c, int g, const uint8_t* rgb, hipStream_t st) {
     auto& tb = c->tb[0];
     ColParams em = bucketed_params(c, 0);
-    em.em_fl = tb.fl; em.em_pb = tb.pb; em.em_n = 0; em.rd_walks = 1;
+    em.em_fl = tb.fl; em.em_pb = tb.pb; em.em_n = 0;
     if (c->stats_m2) { em.em_m2 = 2; em.st_col0 = c->col0_pool; }
-    StageMode md; md.fwd_emit = &em;
+    StageMode md; md.fwd_mode = COLS_EMIT; md.fwd = &em; md.walks = true;
     return enqueue_forward(c, 0, g, rgb, st, md);
 }
 
@@ -2336,7 +2342,7 @@ static int fit_chunk(tfft_ctx* c, int g, const ChunkArgs& a, const uint8_t* cove
     const double gain = ((double)s.PW * (double)s.PH) / ((double)s.W * (double)s.H);
     const unsigned nblk = (unsigned)std::min<uint64_t>(kFitMaxBlocks, (n_bins + 1023) / 1024);
     ColParams ed = bucketed_params(c, 0);
-    ed.em_fl = c->fit_d; ed.em_pb = tb.pb; ed.em_n = 0; ed.rd_walks = 1; ed.em_dsrc = 1;
+    ed.em_fl = c->fit_d; ed.em_pb = tb.pb; ed.em_n = 0;      // (COLS_EMBED_D: em_fl holds the deltas themselves)
     std::vector<unsigned> cnt((size_t)2 * g);
     for (int i = 0; i < g; i++) iters[i] = -1;
     for (int t = 0;; t++) {
@@ -2353,7 +2359,7 @@ static int fit_chunk(tfft_ctx* c, int g, const ChunkArgs& a, const uint8_t* cove
         if (all || t >= max_iters) break;
         // converged images keep their deltas: the inverse gives their bytes again
         HIPCHK(c, launch_fit_correct(tb.ent, tb.fl, tb.pb, jp, c->fit_mu, c->fit_cnt, n_bins, g, gain, c->fit_d, st));
-        StageMode mi; mi.inv_embed = &ed; mi.inv_cover = cover;
+        StageMode mi; mi.inv_mode = COLS_EMBED_D; mi.inv = &ed; mi.walks = true; mi.inv_cover = cover;
         rc = enqueue_inverse(c, 0, g, rgb_out, st, mi);
         if (rc) return rc;
     }
@@ -2684,6 +2690,7 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
     const BucketGeom bg = bucket_geom(c, s, n_images);      // (as embed_chunk and extract_chunk bucket the list)
     { const float2* t; int rc = get_twiddles(c, s.PWi, &t); if (rc) return rc; rc = get_twiddles(c, s.PH, &t); if (rc) return rc; }
     ColParams rd{};
+    bool tile_read = false;      // COLS_FWD_READ: the tile-resident read (else the row-limited step)
     if (stage == COLS_FWD_READ) {
         if (!bins_dev || !index_ok(c, n_bits)) return TFFT_E_INVALID;
         if (c->tile_read && n_bits > 0 && (n_images >= 8 || c->tile_read >= 2)) {
@@ -2693,12 +2700,15 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
             HIPCHK(c, launch_bucket_bins((const tfft_bin*)bins_dev, c->bit_index, n_bits, s.PH, s.PWi, bg.G, c->tb[0].cnt, c->tb[0].off, c->tb[0].ent, c->err, c->tile_read == 2, c->stream));
             rd = bucketed_params(c, 0);
             rd.rd_bits = (uint8_t*)bits_out_dev; rd.rd_n = n_bits;
+            tile_read = true;
         } else {
             HIPCHK(c, launch_bins_last_row((const tfft_bin*)bins_dev, n_bits, s.PH, s.PWi, c->last_row, c->stream));
+            rd.last_row_dev = c->last_row;
         }
     }
     ColParams em{};
-    if ((stage == COLS_INV_A || stage == final_fwd || stage == EMBED || (stage == MEDIANS && tile)) && delta && bits_dev) {
+    const bool delta_lists = (stage == COLS_INV_A || stage == final_fwd || stage == EMBED || (stage == MEDIANS && tile)) && delta && bits_dev;
+    if (delta_lists) {
         if (!index_ok(c, n_bits)) return TFFT_E_STATE;
         int rc = ensure_buckets(c, 0, n_bits, bg.nb, true);
         if (rc) return rc;
@@ -2714,16 +2724,16 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
         // phases of enqueue_forward_tilestats: 2 sample + guess, 4 COLS_STAT, 8 select, 16 tail.  The COLS_STAT step alone needs a bracket
         // (one untimed sample pass); MEDIANS = the whole sequence minus the COLS_STAT launches it contains, timed the same way
         float ms_all = 0.f, ms_stat = 0.f;
-        int rc = enqueue_forward_tilestats(c, 0, n_images, (const uint8_t*)rgb_dev, c->stream, em, tcap, c->usable, 2);
+        int rc = enqueue_forward_tilestats(c, 0, n_images, (const uint8_t*)rgb_dev, c->stream, em, false, tcap, c->usable, 2);
         if (rc) return rc;
         HIPCHK(c, hipEventRecord(c->ev_t0, c->stream));
-        for (int r = 0; r < reps; r++) { rc = enqueue_forward_tilestats(c, 0, n_images, (const uint8_t*)rgb_dev, c->stream, em, tcap, c->usable, 4); if (rc) return rc; }
+        for (int r = 0; r < reps; r++) { rc = enqueue_forward_tilestats(c, 0, n_images, (const uint8_t*)rgb_dev, c->stream, em, false, tcap, c->usable, 4); if (rc) return rc; }
         HIPCHK(c, hipEventRecord(c->ev_t1, c->stream));
         HIPCHK(c, hipEventSynchronize(c->ev_t1));
         HIPCHK(c, hipEventElapsedTime(&ms_stat, c->ev_t0, c->ev_t1));
         if (stage == MEDIANS) {
             HIPCHK(c, hipEventRecord(c->ev_t0, c->stream));
-            for (int r = 0; r < reps; r++) { rc = enqueue_forward_tilestats(c, 0, n_images, (const uint8_t*)rgb_dev, c->stream, em, tcap, c->usable, 2 | 4 | 8 | 16); if (rc) return rc; }
+            for (int r = 0; r < reps; r++) { rc = enqueue_forward_tilestats(c, 0, n_images, (const uint8_t*)rgb_dev, c->stream, em, false, tcap, c->usable, 2 | 4 | 8 | 16); if (rc) return rc; }
             HIPCHK(c, hipEventRecord(c->ev_t1, c->stream));
             HIPCHK(c, hipEventSynchronize(c->ev_t1));
             HIPCHK(c, hipEventElapsedTime(&ms_all, c->ev_t0, c->ev_t1));
@@ -2737,11 +2747,11 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
         switch (stage) {
             case COLS_FWD_A:
             case COLS_FWD_B:
-                { StageMode md; if (em.rd_bins && stage == final_fwd) md.fwd_emit = &em;
+                { StageMode md; if (delta_lists && stage == final_fwd) { md.fwd_mode = COLS_EMIT; md.fwd = &em; }
                   rc = enqueue_fft_stage(c, 0, n_images, stage, (const uint8_t*)rgb_dev, nullptr, c->stream, md); }
                 break;
             case COLS_INV_A:
-                { StageMode md; if (em.rd_bins) md.inv_embed = &em;
+                { StageMode md; if (delta_lists) { md.inv_mode = COLS_EMBED; md.inv = &em; }
                   rc = enqueue_fft_stage(c, 0, n_images, stage, nullptr, nullptr, c->stream, md); }
                 break;
             case ROWS_INV:
@@ -2749,12 +2759,12 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
                   rc = enqueue_fft_stage(c, 0, n_images, stage, nullptr, (uint8_t*)rgb_out_dev, c->stream, md); }
                 break;
             case COLS_FWD_READ:
-                { StageMode md; if (rd.rd_bins) md.fwd_read = &rd; else md.fwd_last_row = c->last_row;
+                { StageMode md; md.fwd_mode = tile_read ? COLS_READ : COLS_ROWLIMIT; md.fwd = &rd;
                   rc = enqueue_fft_stage(c, 0, n_images, final_fwd, nullptr, nullptr, c->stream, md); }
                 break;
             case EMBED: {
                 if (!index_ok(c, n_bits)) return TFFT_E_STATE;
-                if (em.rd_bins) {      // delta embedding: what is left of the embed stage is the gather of the stream bits into bucket order
+                if (delta_lists) {      // delta embedding: what is left of the embed stage is the gather of the stream bits into bucket order
                     HIPCHK(c, launch_gather_bits(c->tb[0].ent, c->tb[0].off + bg.nb, (const uint8_t*)bits_dev, nullptr, nullptr, 0, n_bits, n_bits, n_images, c->tb[0].pb, c->stream));
                     break;
                 }

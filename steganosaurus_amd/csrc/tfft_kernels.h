@@ -25,7 +25,21 @@ struct RowParams {
 // a bin of the list, located inside its column tile: value at LDS row `k` (= y / G), column `c` (= x % 16)
 struct TileBin { uint16_t k; uint8_t c; uint8_t conj; uint32_t bit; };
 
+// The modes of a column step (k_fft_cols; what each does: the comment above the kernel).  The caller of launch_cols names the mode; the
+// groups of ColParams below say which mode reads them
+enum { COLS_PLAIN = 0, COLS_ROWLIMIT = 1, COLS_READ = 2, COLS_EMBED = 3, COLS_EMIT = 4, COLS_STAT = 5, COLS_EMBED_D = 6 };
+constexpr bool embed_mode(int mode) { return mode == COLS_EMBED || mode == COLS_EMBED_D; }      // the first inverse step of a delta embed
+
+// one column step as launch_cols runs it
+struct ColStep {
+    int logl;          // log2 of the column length of the step, <= 9
+    int sign;          // +1 forward, -1 inverse
+    int mode;          // COLS_*
+    bool walks;        // the bucket modes with one walk per image (launch_bucket_walks layout, k_fft_cols<..., PI = true>); false: one shared list
+};
+
 struct ColParams {
+    // every mode: the geometry of the step
     int M;             // columns of the half spectrum (PW/2)
     int PH;            // full column length (twiddle table size)
     int G;             // groups (1 for the direct pass, N2 or N1 for the two-step passes)
@@ -33,21 +47,22 @@ struct ColParams {
     int out_a, out_b;  // output row = out_a*k + out_b*g
     int in_rows;       // input rows >= in_rows are zero (not loaded)
     int out_rows;      // output rows >= out_rows are not stored
-    // extraction straight out of the tiles (k_fft_cols<..., COLS_READ>): the spectrum is never stored
+    // the bucket modes (COLS_READ, COLS_EMIT, COLS_STAT, COLS_EMBED, COLS_EMBED_D): rd_bins, rd_off and trash
+    // COLS_READ, extraction straight out of the tiles (the spectrum is never stored): rd_bits, rd_n
     const struct TileBin* rd_bins;   // bins bucketed by (plane, 16-column tile, group g), see k_bucket_*
     const unsigned* rd_off;          // bucket b = (plane*G + g)*ntiles + tile holds rd_bins[rd_off[b] .. rd_off[b+1])
     uint8_t* rd_bits;                // bits_out, image i at rd_bits + i*rd_n
     uint64_t rd_n;
     uint8_t* trash;                  // >= 8 KiB of device scratch nobody reads: where lanes WITHOUT a list entry send their (unpredicated) stores
-    // delta embedding: the LAST forward step (COLS_EMIT) writes the values of the bucketed bins (rd_bins / rd_off as above) to em_fl
-    // in bucket order; the FIRST inverse step (COLS_EMBED) starts every tile as zeros and puts F' - F at those bins, F taken from
-    // em_fl (S:712-732 with a fixed alpha)
+    // delta embedding: the LAST forward step (COLS_EMIT, COLS_STAT) writes the values of the bucketed bins (rd_bins / rd_off as above) to
+    // em_fl in bucket order; the FIRST inverse step (COLS_EMBED) starts every tile as zeros and puts F' - F at those bins, F taken from
+    // em_fl (S:712-732 with a fixed alpha); COLS_EMBED_D takes F' - F itself from em_fl, in stored coordinates (the fitted embed)
     float2* em_fl;                   // em_n values per image, indexed like rd_bins
     int em_m2;                       // COLS_EMIT: store |F|^2 (float, `out` reinterpreted, same byte offset per image) instead of the complex
                                      // spectrum, the packed column 0 to st_col0: all the statistics read (launch_medians, StatOpts::m2)
     const uint8_t* em_pb;            // COLS_EMBED: em_n stream bits per image in the same order (k_gather_bits; 2 = not written)
-    uint64_t em_n;                   // list stride between images (the length of the bin list; 0 with rd_walks, whose entry indices are absolute)
-    float em_cos, em_sin;
+    uint64_t em_n;                   // list stride between images (the length of the bin list; 0 with ColStep::walks, whose entry indices are absolute)
+    float em_cos, em_sin;            // COLS_EMBED
     // phase options of the batched calls (tfft_set_phase_options); COLS_EMBED and COLS_READ only
     const float2* em_jp;             // jitter as unit phasors (cos j, sin j), indexed like rd_bins (shared by all images); nullptr = no jitter
     const float* em_med;             // COLS_EMBED, adaptive alpha: 3 medians |F| per image of the launch; nullptr = the fixed em_cos / em_sin
@@ -63,7 +78,7 @@ struct ColParams {
     float* st_amb;
     float2* st_col0;                 // per (image, plane) PH values
     unsigned st_slo, st_shi;         // squared radius bounds of the annulus, clamped to 32 bits
-    int st_cap, st_PW;
+    int st_cap, st_PW;               // (st_PW: written, not read)
     // forward COLS_PLAIN only: a sample of the tiles (0, tile_step, 2*tile_step, ..) written side by side into a narrow spectrum
     int tile_step, tile_off; int out_M; size_t out_plane_stride, out_img_stride;      // tiles tile_off + i*tile_step
     // forward COLS_PLAIN only: images whose statistics were settled without the spectrum (all three planes) return at once
@@ -72,19 +87,17 @@ struct ColParams {
     // top 13 bits of the float, weight 2) kept in LDS at byte offset hist_lds_off and added to hist_sel[3*img + plane].hist at the end
     struct SelectState* hist_sel; unsigned hist_lds_off;
     int g_step, g_off;          // ... and only the row groups g_off + i*g_step of the launch (0: all): rows g + G*k, a regular subsample of the rows
-    int em_on;
-    // DC removal (forward, final step only): out[row][col] += dc_ah[row] * dc_aw[col] -- the transform of the constant that
-    // the row kernels subtracted from the pixels, c*A_H(y)*A_W(x); nullptr = off
+    // DC removal (every forward mode, final step only; inverse: COLS_PLAIN, first step): out[row][col] += dc_ah[row] * dc_aw[col] -- the
+    // transform of the constant that the row kernels subtracted from the pixels, c*A_H(y)*A_W(x); nullptr = off
     const float2* dc_ah;       // PH entries, the factor c included
     const float2* dc_aw;       // M entries, entry 0 packed: A_W(0) + i*A_W(M)
-    const int* last_row_dev;   // optional device scalar: rows > *last_row_dev are not stored either (extraction reads
+    const int* last_row_dev;   // COLS_ROWLIMIT: device scalar, rows > *last_row_dev are not stored either (extraction reads
                                // only the rows its bin list touches; k_bins_last_row)
+    // every mode
     int tw_out;        // multiply output by exp(sign*2*pi*i*k*g/PH)
     int tiles_per_block;  // adjacent 16-column tiles walked by one workgroup
     size_t plane_stride;  // float2 elements between planes (PH*M)
     size_t img_stride;    // float2 elements between images (grid.z = 3*n_images)
-    int rd_walks;         // the bucket modes with one walk per image (launch_bucket_walks layout, k_fft_cols<..., PI = true>); 0 = one shared list
-    int em_dsrc;          // first inverse step of a walks embed: em_fl holds F' - F itself, in stored coordinates (COLS_EMBED_D, the fitted embed)
 };
 
 struct EmbedParams {
@@ -190,8 +203,7 @@ hipError_t launch_colrow_inv(const float2* in, uint8_t* rgb, const float2* tw_pw
 hipError_t launch_rowcol_fwd_live(const uint8_t* rgb, float2* out, const float2* tw_pw, const float2* tw_ph, const RowParams& P, int n_images, hipStream_t s);
 hipError_t launch_rows_inv(const float2* in, uint8_t* rgb, const float2* tw_pw, const RowParams& P, int n_images,
                            hipStream_t s);
-hipError_t launch_cols(const float2* in, float2* out, const float2* tw_ph, const ColParams& P, int logl, int sign,
-                       int n_planes, hipStream_t s);
+hipError_t launch_cols(const float2* in, float2* out, const float2* tw_ph, const ColParams& P, const ColStep& step, int n_planes, hipStream_t s);
 // (f-4) fp64 audit transform, tfft_audit64.hip
 hipError_t audit_fft2d_f64(double2* a, double2* scratch, double2* wtab, int n_planes, int PH, int PW, int inverse, hipStream_t s);
 hipError_t audit_load_rgb8_f64(const uint8_t* rgb_dev, int W, int H, int PW, int PH, int center, double2* out, hipStream_t s);

@@ -872,7 +872,8 @@ __device__ __forceinline__ unsigned opaque_u32(unsigned v) {
 constexpr int cols_threads(int logl) { return imax(256, 16 * ((1 << logl) / elems_for(1 << logl))); }
 __device__ __forceinline__ int read_bit_value(float2 v, const EmbedParams& P, int p, const float* __restrict__ jitter, uint64_t j);   // defined with k_read
 
-// MODE (own symbols, so that a kernel trace tells them apart):
+// MODE (the COLS_* of tfft_kernels.h, named by the caller of launch_cols in its ColStep; own symbols, so that a kernel trace tells them
+// apart; which combinations with the switches below exist: cols_variant_exists):
 //   COLS_PLAIN     the transform
 //   COLS_ROWLIMIT  rows above *P.last_row_dev are not stored
 //   COLS_READ      extraction: nothing is stored at all -- the tile is parked in LDS and the bits of the bins
@@ -889,8 +890,6 @@ __device__ __forceinline__ int read_bit_value(float2 v, const EmbedParams& P, in
 //   COLS_EMBED_D   COLS_EMBED with F' - F not computed from (F, bit, alpha) but taken as it is from P.em_fl: one value per bucket entry,
 //                  in the coordinates of the stored bin -- the corrected deltas of the fitted embed (tfft_embed_stream_batch_fit_dev,
 //                  DESIGN.md section 10).  One walk per image only (PI)
-enum { COLS_PLAIN = 0, COLS_ROWLIMIT = 1, COLS_READ = 2, COLS_EMBED = 3, COLS_EMIT = 4, COLS_STAT = 5, COLS_EMBED_D = 6 };
-constexpr bool embed_mode(int mode) { return mode == COLS_EMBED || mode == COLS_EMBED_D; }      // the first inverse step of a delta embed
 __device__ __forceinline__ unsigned frame_bit(const uint8_t* __restrict__ header, const uint8_t* __restrict__ payload, uint64_t i);   // defined with k_embed
 // DC: the DC-removal epilogue (ColParams::dc_*) is compiled in; its own instantiation, because the kernel sits at the
 // 256-VGPR cap and even the unused code costs accumulation-register spills
@@ -2325,68 +2324,55 @@ static hipError_t launch_cols_t(const float2* in, float2* out, const float2* tw,
     hipLaunchKernelGGL(k, grid, block, lds_total, s, in, out, tw, Q);
     return hipGetLastError();
 }
-// one walk per image (ColParams::rd_walks): the bucket modes with PI, the same choices as below.  launch_cols checked the fields
-static hipError_t launch_cols_walks(const float2* in, float2* out, const float2* tw_ph, const ColParams& P, int logl, int sign,
-                                    int n_planes, hipStream_t s) {
-    if (!P.rd_bins) return hipErrorInvalidValue;
-    const bool phase = P.em_jp || P.em_med;
-#define L_(n, MODE, DCF, TWF, PHF) launch_cols_t<(n <= 9 ? n : 9), (embed_mode(MODE) ? -1 : +1), MODE, DCF, TWF, false, PHF, true>(in, out, tw_ph, P, n_planes, s)
-#define GW(n, MODE, PHF) (P.dc_ah ? L_(n, MODE, true, false, PHF) : L_(n, MODE, false, false, PHF))
-#define F(n)                                                                                                             \
-    return sign < 0 ? (P.em_dsrc ? (P.tw_out ? L_(n, COLS_EMBED_D, false, true, false) : L_(n, COLS_EMBED_D, false, false, false))   \
-                      : phase ? (P.tw_out ? L_(n, COLS_EMBED, false, true, true) : L_(n, COLS_EMBED, false, false, true))   \
-                              : (P.tw_out ? L_(n, COLS_EMBED, false, true, false) : L_(n, COLS_EMBED, false, false, false))) \
-         : (P.em_on && P.st_sel) ? GW(n, COLS_STAT, false) : P.em_on ? GW(n, COLS_EMIT, false)                            \
-         : P.em_jp ? GW(n, COLS_READ, true) : GW(n, COLS_READ, false)
-    TFFT_DISPATCH_LOG(logl, F)
-#undef F
-#undef GW
-#undef L_
-    return hipSuccess;
+// Which instantiations of k_fft_cols exist (FULL aside, which launch_cols_t picks): the guard of the dispatch below, so also what
+// launch_cols accepts.  The inverse knows the plain step and the first step of a delta embed (no DC term: the tile holds F' - F);
+// every other mode belongs to the final forward step (no output twiddles), the plain forward step is the final one (DC) or the
+// first of two (TW).  PH: COLS_EMBED and COLS_READ only; PI: the bucket modes, COLS_EMBED_D in no other form
+constexpr bool cols_variant_exists(int mode, int sign, bool dc, bool tw, bool ph, bool pi) {
+    if (sign < 0) return mode == COLS_PLAIN ? !ph && !pi : mode == COLS_EMBED ? !dc : mode == COLS_EMBED_D ? !dc && !ph && pi : false;
+    switch (mode) {
+        case COLS_PLAIN: return !(dc && tw) && !ph && !pi;
+        case COLS_ROWLIMIT: return !tw && !ph && !pi;
+        case COLS_READ: return !tw;
+        case COLS_EMIT: case COLS_STAT: return !tw && !ph;
+        default: return false;
+    }
 }
-hipError_t launch_cols(const float2* in, float2* out, const float2* tw_ph, const ColParams& P, int logl, int sign,
-                       int n_planes, hipStream_t s) {
-    if (logl > 9) return hipErrorInvalidValue;      // 512 x 16 x 8 B tiles: two workgroups per CU; plan_cols never asks for more
-    if ((P.last_row_dev || (P.rd_bins && !P.em_on)) && sign < 0) return hipErrorInvalidValue;      // both variants exist for the forward direction only
-    if (P.em_on && (!P.rd_bins || (sign < 0 && P.dc_ah) || (sign > 0 && P.last_row_dev))) return hipErrorInvalidValue;      // delta embedding: EMIT (forward, final step) / EMBED (inverse, first step, DC term absent)
-    if (P.tw_out && sign > 0 && (P.dc_ah || P.rd_bins || P.last_row_dev)) return hipErrorInvalidValue;      // forward variants belong to the final step (no output twiddle)
-    if (P.em_on && !P.em_fl) return hipErrorInvalidValue;
-    if (P.rd_bins && !P.trash) return hipErrorInvalidValue;
-    if (P.st_sel && (!P.em_on || sign < 0 || logl > 9 || logl < 4 || !P.st_cand || !P.st_col0 || (P.st_cap && (!P.st_partial || !P.st_amb)))) return hipErrorInvalidValue;
-    if ((P.tile_step > 1 || P.gate) && (sign < 0 || P.rd_bins || P.last_row_dev || P.tw_out)) return hipErrorInvalidValue;      // plain final forward step only       // the bucket modes redirect the stores of idle lanes to the context's scratch line
-    if (P.em_m2 && sign > 0 && (!P.em_on || !P.st_col0)) return hipErrorInvalidValue;      // (the inverse step ignores it)
-    // the phase options exist in the first inverse step (COLS_EMBED) and the tile-resident read (COLS_READ) only
-    if ((P.em_jp || P.em_med) && !((sign < 0 && P.em_on) || (sign > 0 && P.rd_bins && !P.em_on))) return hipErrorInvalidValue;
-    if (P.em_med && sign > 0) return hipErrorInvalidValue;
-    if (P.em_dsrc && !(sign < 0 && P.em_on && P.rd_walks && !P.em_jp && !P.em_med)) return hipErrorInvalidValue;      // COLS_EMBED_D: walks, no phase options
-    const bool phase = P.em_jp || P.em_med;
-    if (P.rd_walks) return launch_cols_walks(in, out, tw_ph, P, logl, sign, n_planes, s);
-#define G(n, MODE)                                                                      \
-    (P.dc_ah ? launch_cols_t<(n <= 9 ? n : 9), +1, MODE, true>(in, out, tw_ph, P, n_planes, s) \
-             : launch_cols_t<(n <= 9 ? n : 9), +1, MODE, false>(in, out, tw_ph, P, n_planes, s))
-#define GI(n, DCF)                                                                      \
-    (P.tw_out ? launch_cols_t<(n <= 9 ? n : 9), -1, COLS_PLAIN, DCF, true>(in, out, tw_ph, P, n_planes, s) \
-              : launch_cols_t<(n <= 9 ? n : 9), -1, COLS_PLAIN, DCF, false>(in, out, tw_ph, P, n_planes, s))
-#define GE(n)                                                                      \
-    (phase ? (P.tw_out ? launch_cols_t<(n <= 9 ? n : 9), -1, COLS_EMBED, false, true, false, true>(in, out, tw_ph, P, n_planes, s) \
-                       : launch_cols_t<(n <= 9 ? n : 9), -1, COLS_EMBED, false, false, false, true>(in, out, tw_ph, P, n_planes, s)) \
-           : P.tw_out ? launch_cols_t<(n <= 9 ? n : 9), -1, COLS_EMBED, false, true>(in, out, tw_ph, P, n_planes, s) \
-                      : launch_cols_t<(n <= 9 ? n : 9), -1, COLS_EMBED, false, false>(in, out, tw_ph, P, n_planes, s))
-#define GR(n)                                                                      \
-    (!P.em_jp ? G(n, COLS_READ)                                                    \
-              : P.dc_ah ? launch_cols_t<(n <= 9 ? n : 9), +1, COLS_READ, true, false, false, true>(in, out, tw_ph, P, n_planes, s) \
-                        : launch_cols_t<(n <= 9 ? n : 9), +1, COLS_READ, false, false, false, true>(in, out, tw_ph, P, n_planes, s))
-#define F(n)                                                                            \
-    return sign < 0 ? (P.em_on ? GE(n) : P.dc_ah ? GI(n, true) : GI(n, false)) \
-         : P.tw_out ? launch_cols_t<(n <= 9 ? n : 9), +1, COLS_PLAIN, false, true>(in, out, tw_ph, P, n_planes, s) \
-         : (P.em_on && P.st_sel) ? G(n, COLS_STAT) : P.em_on ? G(n, COLS_EMIT) : P.rd_bins ? GR(n) : P.last_row_dev ? G(n, COLS_ROWLIMIT) : G(n, COLS_PLAIN)
-    TFFT_DISPATCH_LOG(logl, F)
-#undef F
-#undef G
-#undef GI
-#undef GE
-#undef GR
-    return hipSuccess;
+// a run-time value lo <= v <= hi as a compile-time one: f(std::integral_constant<int, v>).  launch_cols nests four of these, so the
+// innermost body exists 10 x 2 x 7 x 16 times on the host; where cols_variant_exists says no, that body is `return hipErrorInvalidValue`
+// alone and names no kernel, so only the existing forms are instantiated.  (The row launchers' sizes go through TFFT_DISPATCH_LOG.)
+template <int LO, int HI, class F>
+static hipError_t with_constant(int v, const F& f) {
+    if constexpr (LO > HI) return hipErrorInvalidValue;
+    else return v == LO ? f(std::integral_constant<int, LO>{}) : with_constant<LO + 1, HI>(v, f);
+}
+hipError_t launch_cols(const float2* in, float2* out, const float2* tw_ph, const ColParams& P, const ColStep& step, int n_planes, hipStream_t s) {
+    const int mode = step.mode;
+    const bool fwd = step.sign > 0, emit = mode == COLS_EMIT || mode == COLS_STAT, buckets = emit || embed_mode(mode) || mode == COLS_READ;
+    if (step.logl > 9) return hipErrorInvalidValue;      // 512 x 16 x 8 B tiles: two workgroups per CU; plan_cols never asks for more
+    // what the mode reads (the bucket modes redirect the stores of idle lanes to the context's scratch line)
+    if (buckets && (!P.rd_bins || !P.trash)) return hipErrorInvalidValue;
+    if ((emit || embed_mode(mode)) && !P.em_fl) return hipErrorInvalidValue;
+    if (mode == COLS_ROWLIMIT && !P.last_row_dev) return hipErrorInvalidValue;
+    if (mode == COLS_STAT && (step.logl < 4 || !P.st_sel || !P.st_cand || !P.st_col0 || (P.st_cap && (!P.st_partial || !P.st_amb)))) return hipErrorInvalidValue;
+    // fields that change what a launch does, in the one mode that honours them
+    if (P.em_m2 && fwd && !(emit && P.st_col0)) return hipErrorInvalidValue;      // |F|^2 planes: COLS_EMIT (COLS_STAT stores nothing, the inverse step ignores it)
+    if ((P.tile_step > 1 || P.gate) && !(mode == COLS_PLAIN && fwd && !P.tw_out)) return hipErrorInvalidValue;      // plain final forward step only
+    if (P.em_med && mode != COLS_EMBED) return hipErrorInvalidValue;      // adaptive alpha: the embedding step only (COLS_READ knows the jitter alone)
+    // DC: ColParams::dc_ah, TW: tw_out, PH: the phase options, PI: one walk per image
+    const int sw = (P.dc_ah ? 1 : 0) | (P.tw_out ? 2 : 0) | (P.em_jp || P.em_med ? 4 : 0) | (step.walks ? 8 : 0);
+    return with_constant<0, 9>(step.logl, [&](auto logl) {
+        return with_constant<0, 1>(fwd ? 1 : 0, [&](auto f) {
+            return with_constant<COLS_PLAIN, COLS_EMBED_D>(mode, [&](auto m) {
+                return with_constant<0, 15>(sw, [&](auto w) {
+                    constexpr int LOGL = decltype(logl)::value, SIGN = decltype(f)::value ? +1 : -1, MODE = decltype(m)::value, SW = decltype(w)::value;
+                    constexpr bool DC = SW & 1, TW = SW & 2, PH = SW & 4, PI = SW & 8;
+                    if constexpr (cols_variant_exists(MODE, SIGN, DC, TW, PH, PI)) return launch_cols_t<LOGL, SIGN, MODE, DC, TW, false, PH, PI>(in, out, tw_ph, P, n_planes, s);
+                    else return hipErrorInvalidValue;
+                });
+            });
+        });
+    });
 }
 
 hipError_t launch_bucket_bins(const tfft_bin* bins, const uint32_t* bit_index, uint64_t n, int PH, int PW, int G,

@@ -30,6 +30,12 @@ def test_same_lists_give_the_shared_list_bytes_chunk_of_nine(emu, orc):
                         envs=({}, {"TFFT_STREAMS": "2"}, {"TFFT_TILE_READ": "0"}, {"TFFT_STATS_TILE": "2"}), host=False)
 
 
+def test_same_lists_without_jitter_chunk_of_eight(emu, orc):
+    # Eight images in one chunk take the tile-resident read by default; without jitter that is the per-image read with no phase options
+    # (k_fft_cols<.., COLS_READ, PH = false, PI = true>), which no other case here launches.  128 x 128: the direct column plan
+    WC.check_same_lists(emu, orc, HostBufs, 128, 128, nimg=8, slots=8, secret=8, jitter=0.0, adaptive=False, envs=({},), host=False)
+
+
 @pytest.mark.parametrize("jitter,adaptive", [(0.0, False), (0.05, False), (0.0, True), (0.05, True)])
 def test_distinct_keys_two_step_columns(emu, orc, jitter, adaptive):
     # PH = 512: the two-step column plan, buckets per (image, plane, row group, column tile)

@@ -43,6 +43,11 @@ def test_same_lists_1080p_chunks_of_three(lib, orc):
                         envs=({}, {"TFFT_TILE_READ": "0"}, {"TFFT_TILE_READ": "3"}, {"TFFT_STATS_TILE": "0"}, {"TFFT_EMBED_DELTA": "0"}))
 
 
+def test_same_lists_without_jitter_chunk_of_eight(lib, orc):
+    # the twin of the emulated case: the direct column plan, the per-image tile-resident read without phase options
+    WC.check_same_lists(lib, orc, PC.TorchBufs, 128, 128, nimg=8, slots=8, secret=8, jitter=0.0, adaptive=False, envs=({},), host=False)
+
+
 def test_same_lists_4k(lib, orc):
     WC.check_same_lists(lib, orc, PC.TorchBufs, 3840, 2160, nimg=3, slots=3, secret=200, jitter=0.05, adaptive=True,
                         envs=({}, {"TFFT_STATS_TILE": "0"}, {"TFFT_TILE_READ": "0"}))
