@@ -2297,6 +2297,7 @@ static hipError_t launch_cols_t(const float2* in, float2* out, const float2* tw,
     constexpr bool BUCKETS = (MODE == COLS_READ || embed_mode(MODE) || MODE == COLS_EMIT || MODE == COLS_STAT);
     if (BUCKETS) {          // the bucket offsets of a workgroup's tiles are staged in LDS: 16 tiles + sentinel per group
         if (tpb > 16) tpb = 16;
+        if (tpb > ntiles) tpb = ntiles;      // a grid narrower than the request: COLS_STAT's reservations (st_resv) go with the tiles a workgroup really has
         Q.tiles_per_block = tpb;
     }
     const size_t nwaves = ((size_t)C * T * gpb + 63) / 64;

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import parity_cases as PC
+import plan_matrix_cases as PM
 from steganosaurus_amd import binding as B
 
 EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
@@ -292,32 +293,9 @@ def test_tile_resident_extraction_over_the_column_plans(emu, orc, wh):
     """Spectrum-free batched extraction (bins bucketed per tile, bits read in LDS by the last forward column step)
     against the spectrum + k_read path for a two-step column plan (PH = 512), the fused rows+columns plan
     (PW = 2048) and a direct plan whose half width is not a multiple of the 16-column tile."""
-    from steganosaurus_amd.synth import cover_rgb
     w, h = wh
-    nimg, n = 2, 200
-    ph, pw = orc.next_pow2(h), orc.next_pow2(w)
     # rmax = 0.95: part of the walk lies in the mirror half (x > PW/2), stored conjugated at (PH-y, PW-x)
-    bins = B.Walk(orc.subkeys(PC.PK)[0], ph, pw, rmin=0.05, rmax=0.95, lib=emu).next(n)
-    if ph >= 4 * pw:        # tall grid: the annulus reaches beyond PW/2
-        assert (bins["x"] > pw // 2).any() and (bins["x"] < pw // 2).any()
-    sbins, idx = B.bins_sort(bins, lib=emu)
-    imgs = np.stack([cover_rgb(w, h, 20 + i) for i in range(nimg)])
-    res = []
-    for mode, bl, index in (("3", sbins, idx), ("0", sbins, idx), ("3", bins, None), ("2", bins, None)):
-        os.environ["TFFT_TILE_READ"] = mode
-        try:
-            ctx = B.Context(w, h, slots=nimg, lib=emu)
-        finally:
-            del os.environ["TFFT_TILE_READ"]
-        if index is not None:
-            ctx.set_bit_index(index)
-        raw = np.full((nimg, n), 9, np.uint8)
-        ctx.extract_batch_dev(nimg, imgs.ctypes.data, w, h, bl.ctypes.data, n, raw.ctypes.data)
-        ctx.sync(); ctx.close()
-        res.append(raw)
-    for r in res[1:]:
-        assert np.array_equal(r, res[0])
-    assert set(np.unique(res[0])) <= {0, 1}
+    PM.check_tile_read(emu, orc, PC.HostBufs, w, h, nimg=2, n=200, rmin=0.05, rmax=0.95)
 
 
 @pytest.mark.parametrize("case", [dict(w=40, h=24, n_bits=150), dict(w=40, h=300, n_bits=300, rmax=0.95), dict(w=2040, h=130, n_bits=300, nimg=1),

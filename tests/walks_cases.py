@@ -118,17 +118,21 @@ def check_same_lists(lib, orc, bufs, w, h, nimg, slots, secret=8, jitter=0.05, a
 
 
 def check_distinct_keys(lib, orc, bufs, w, h, nimg, slots, secret=8, jitter=0.05, adaptive=False, center=False, n_oracle=None,
-                        lsb_frac=0.05, envs=({},), n_threads=4):
+                        lsb_frac=0.05, envs=({},), n_threads=4, rmin=0.05, rmax=0.45, pks=None):
     """every image with its own key: each stego within the LSB bar of the fp64 reference's embed with that image's own walk, the raw
     bits read from the reference's stego equal the reference's on every stream position (beyond the stream only bins on the decision
     line may differ), payloads round-trip (power-of-two covers), and image i read with image j's walk is "Magic not found" (-1)"""
-    P = Params(jitter=jitter, adaptive_alpha=int(adaptive), center=int(center))
+    P = Params(jitter=jitter, adaptive_alpha=int(adaptive), center=int(center), rmin=rmin, rmax=rmax)
     plen = secret + 16
     n_str = 912 + 56 * plen
     n_bins = n_str + 300
     ph, pw = orc.next_pow2(h), orc.next_pow2(w)
-    pks, keys = image_keys(orc, nimg)
-    bins, jit, st = B.walks_build(keys, ph, pw, n_bins, max_jitter=jitter if jitter else None, n_threads=n_threads, lib=lib)
+    if pks is None:
+        pks, keys = image_keys(orc, nimg)
+    else:           # the caller's own path keys, one per image
+        assert len(pks) == nimg
+        keys = b"".join(b"".join(orc.subkeys(pk)) for pk in pks)
+    bins, jit, st = B.walks_build(keys, ph, pw, n_bins, max_jitter=jitter if jitter else None, rmin=rmin, rmax=rmax, n_threads=n_threads, lib=lib)
     assert (st == 0).all()
     covers = np.stack([cover_rgb(w, h, 500 + i) for i in range(nimg)])
     headers, payloads = _frames(nimg, secret, 70)
