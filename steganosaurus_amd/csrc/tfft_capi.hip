@@ -1521,8 +1521,6 @@ static int gather_jitter(tfft_ctx* c, int which, uint64_t n_bits, int nb, hipStr
     return TFFT_OK;
 }
 
-// one chunk (slots [s0, s0+g), equal geometry) of the two batched pipelines
-// forward transform + statistics of slots [s0, s0+g) without a stored spectrum (see ColParams::st_*): em carries the delta-embedding lists
 // the statistics' side stream: lowest priority, so that its small kernels fill gaps instead of taking workgroup slots from the transform
 // they run beside (TFFT_STATS_PRIO=0: default priority)
 static hipError_t create_stats_stream(tfft_ctx* c, hipStream_t* out) {
@@ -1587,6 +1585,7 @@ static int enqueue_tilestats_tail(tfft_ctx* c, int s0, int g, const uint8_t* rgb
     return TFFT_OK;
 }
 
+// forward transform + statistics of slots [s0, s0+g) without a stored spectrum (see ColParams::st_*): em carries the delta-embedding lists
 // phases (tfft_profile_stage times them apart): 1 the steps before the last column step, 2 sample + bracket guess, 4 the COLS_STAT step,
 // 8 select, 16 gated spectrum + fallbacks + capacity
 static int enqueue_forward_tilestats(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, hipStream_t st, const ColParams& em, bool walks,
@@ -1663,126 +1662,148 @@ static int build_buckets_walks(tfft_ctx* c, int which, const tfft_bin* bins, uin
     HIPCHK(c, launch_gather_jitter_walks(tb.ent, jit, n_bits, g, tb.jp, st));
     return TFFT_OK;
 }
+// ---- Which launch sequence a chunk takes.  Decided once, by the functions below, for the pipelines (embed_chunk, extract_chunk, fit_chunk)
+// and for tfft_profile_stage alike: nobody else reads the knobs these look at (DESIGN.md section 4 has the table)
+// the compute stream a chunk runs on: 0 the context's, 1 the one of the second half of a split chunk (TFFT_STREAMS=2)
+static int stream_index(const tfft_ctx* c, hipStream_t st) { return (c->stream2 && st == c->stream2) ? 1 : 0; }
+// adaptive alpha and jitter of a chunk: the per-image calls bring their own, the shared-list calls have the context's phase options
+// (rc: the shared-list state does not mix with per-image walks)
+struct PhaseOpts { int rc; bool adaptive; const float* jit; };
+static PhaseOpts phase_opts(const tfft_ctx* c, const ChunkArgs& a) {
+    if (!a.per_image) return PhaseOpts{TFFT_OK, c->ph_adaptive != 0, c->ph_jit};
+    return PhaseOpts{(c->bit_index || c->ph_jit) ? TFFT_E_STATE : TFFT_OK, a.adaptive, a.jit};
+}
+// the statistics of an embed: none; the bracket pass inside the last forward step (COLS_STAT), then select chain and gated tail; medians +
+// capacity in one sequence over the stored planes; medians, then the capacity as a pass of its own
+enum StatsForm { STATS_NONE, STATS_IN_STEP, STATS_FUSED, STATS_SEPARATE };
+// what the last forward column step leaves in `spec` (= ColParams::em_m2): the spectrum, |F|^2 planes + the packed column 0, nothing.  (A
+// COLS_STAT step stores nothing and takes 0: the spectrum, where a plane needs it after all, comes from the gated plain step of the tail)
+enum FwdStore { STORE_SPEC = 0, STORE_M2 = 1, STORE_NONE = 2 };
+// delta: stego = cover + IFFT(F' - F) from the bucketed lists (else F' is written into the spectrum, k_embed, and inverted); side: the
+// statistics run on the side stream, beside the inverse transform
+struct EmbedPath { bool delta; StatsForm stats; FwdStore store; bool side; };
+// stats: the chunk runs the statistics (capacities asked for, or adaptive alpha: see embed_chunk)
+static EmbedPath embed_path(const tfft_ctx* c, const Slot& s, int g, const ChunkArgs& a, bool stats) {
+    // (delta whatever the chunk size: the bytes of a stego image do not depend on how the batch was cut)
+    EmbedPath p{c->embed_delta && a.alpha > 0.0 && a.alpha < M_PI && a.n_bits > 0, STATS_NONE, STORE_SPEC, false};
+    if (!stats && p.delta && c->stats_m2) p.store = STORE_NONE;      // nobody reads the spectrum of a delta embed
+    if (!stats) return p;
+    const CapParams cap = cap_params(c, s, a.rmin, a.rmax);
+    p.stats = (c->stats_fused && cap.bw > 0) ? STATS_FUSED : STATS_SEPARATE;
+    if (!p.delta) return p;      // (the embed reads the medians' spectrum: everything in line)
+    if (tilestats_applies(c, s, plan_cols(c, s.PH, s.PWi, g), cap, g)) p.stats = STATS_IN_STEP;
+    else if (stats_m2_applies(c, s, cap)) p.store = STORE_M2;
+    p.side = c->stats_async && !phase_opts(c, a).adaptive;      // (adaptive: the embed waits for the medians)
+    return p;
+}
+// The spectrum is only ever read at the bins of the list.  READ_TILES: the bins bucketed by column tile, the last forward column step reads
+// the bits out of its LDS-resident tiles -- no spectrum store, no k_read.  READ_ROWLIMIT: rows above the list's highest are not stored, then k_read
+enum ReadForm { READ_TILES, READ_ROWLIMIT };
+// (the bucket build is per call: it pays off from about 8 images per chunk; TFFT_TILE_READ=2/3 force it)
+// registered: the list keeps its buckets (no per-call build to pay for): then the tile-resident read also serves small chunks of LARGE
+// images (one 4K image: 0.739 -> 0.725 ms per round trip; one 1080p image has too few tiles to fill the chip: 0.265 -> 0.301)
+// (an alpha outside (0, pi) takes the general phase comparison of k_read: the tile kernel reads the sign of Im only)
+static ReadForm read_form(const tfft_ctx* c, const Slot& s, int g, const ChunkArgs& a, bool registered) {
+    const bool reg_large = registered && (unsigned long long)s.PH * s.PWi >= (1ull << 23);
+    const bool tiles = c->tile_read && a.n_bits > 0 && a.alpha > 0.0 && a.alpha < M_PI && (g >= 8 || c->tile_read >= 2 || reg_large);
+    return tiles ? READ_TILES : READ_ROWLIMIT;
+}
+
+// Delta embedding.  The inverse transform is linear and IFFT(F) is the cover itself, so the stego image is cover + IFFT(F' - F),
+// and F' - F is zero but for the bins of the list.  The bins are bucketed by column tile (the buckets extraction uses); the last
+// forward column step, which has every tile in LDS, writes the values of the listed bins out in bucket order; the first inverse
+// column step builds its tiles from that list instead of reading the spectrum; nothing writes F' anywhere, and the row kernel adds
+// its result to the cover's pixels.  (The bucket build is per call unless the list is registered, tfft_bins_register_dev.)
+// (jitter and adaptive alpha ride along: the entries carry the jitter phasor and the image's medians scale alpha)
+// One sequence for every path: lists, forward, fork, statistics, embed + inverse, join, the in-kernel statistics' tail
 static int embed_chunk_impl(tfft_ctx* c, int s0, int g, hipStream_t st, const ChunkArgs& a, const uint8_t* rgb_in, unsigned long long* usable,
                             uint8_t* rgb_out) {
     const Slot& s = c->slots[s0];
     const uint64_t n_bits = a.n_bits;
-    const double alpha = a.alpha;
     const bool walks = a.per_image;
     if (!index_ok(c, n_bits) || !phase_ok(c, n_bits)) return TFFT_E_STATE;
-    if (walks && (c->bit_index || c->ph_jit)) return TFFT_E_STATE;      // (the shared-list state does not mix with per-image walks)
-    const bool adaptive = walks ? a.adaptive : c->ph_adaptive != 0;
-    const float* jit = walks ? a.jit : c->ph_jit;
-    EmbedParams ep = embed_params(c, s, n_bits, alpha, adaptive, nullptr, jit != nullptr);
+    const PhaseOpts ph = phase_opts(c, a);
+    if (ph.rc) return ph.rc;
+    const EmbedPath path = embed_path(c, s, g, a, usable != nullptr);
+    const bool in_step = path.stats == STATS_IN_STEP;
+    EmbedParams ep = embed_params(c, s, n_bits, a.alpha, ph.adaptive, nullptr, ph.jit != nullptr);
     if (walks) ep.bins_stride = n_bits;
-    if (adaptive) ep.med_dev = c->med + 3 * s0;      // (the statistics below run before the embed: see `async`)
+    if (ph.adaptive) ep.med_dev = c->med + 3 * s0;      // (the statistics below run before the embed: see EmbedPath::side)
     if (a.limit < n_bits) ep.limit = a.limit;      // the stream is shorter than the bin list (image i's bits still n_bits apart)
     if (a.framed()) { ep.frame_hdr = a.hdr; ep.frame_pay = a.pay; ep.frame_plen = a.plen; }
-    // Delta embedding.  The inverse transform is linear and IFFT(F) is the cover itself, so the stego image is cover + IFFT(F' - F),
-    // and F' - F is zero but for the bins of the list.  The bins are bucketed by column tile (the buckets extraction uses); the last
-    // forward column step, which has every tile in LDS, writes the values of the listed bins out in bucket order; the first inverse
-    // column step builds its tiles from that list instead of reading the spectrum; nothing writes F' anywhere, and the row kernel adds
-    // its result to the cover's pixels.  (The bucket build is per call unless the list is registered, tfft_bins_register_dev.)
-    // (jitter and adaptive alpha ride along: the entries carry the jitter phasor and the image's medians scale alpha)
-    const bool delta = c->embed_delta && alpha > 0.0 && alpha < M_PI && n_bits > 0;      // whatever the chunk size: the bytes of a stego image do not depend on how the batch was cut
-    const int which = (c->stream2 && st == c->stream2) ? 1 : 0;
+    CapParams cap = cap_params(c, s, a.rmin, a.rmax);
+    cap.magmin = a.magmin;
+    const int which = stream_index(c, st);
     ColParams em{};
     int rc;
-    if (delta) {
+    if (path.delta) {      // the lists of the chunk in bucket order
         const BucketGeom bg = bucket_geom(c, s, g);
-        const int nb = bg.nb;
-        rc = ensure_buckets(c, which, n_bits, nb, true);
+        rc = ensure_buckets(c, which, n_bits, bg.nb, true);
         if (rc) return rc;
-        rc = walks ? build_buckets_walks(c, which, a.bins, n_bits, g, s, bg, jit, st) : build_buckets(c, which, a.bins, n_bits, s, bg.G, st);
+        rc = walks ? build_buckets_walks(c, which, a.bins, n_bits, g, s, bg, ph.jit, st) : build_buckets(c, which, a.bins, n_bits, s, bg.G, st);
         if (rc) return rc;
         auto& tb = c->tb[which];
         em = bucketed_params(c, which);
         em.em_fl = tb.fl + (size_t)s0 * n_bits; em.em_pb = tb.pb + (size_t)s0 * n_bits;
         em.em_n = walks ? 0 : n_bits; em.em_cos = ep.cos_a; em.em_sin = ep.sin_a;      // (walks: entry indices are absolute)
-        if (!walks) rc = gather_jitter(c, which, n_bits, nb, st);
+        if (!walks) rc = gather_jitter(c, which, n_bits, bg.nb, st);
         if (rc) return rc;
-        em.em_jp = jit ? tb.jp : nullptr;
-        em.em_med = adaptive ? c->med + 3 * s0 : nullptr; em.em_alpha = (float)alpha;
-        if (usable) {
-            CapParams p0 = cap_params(c, s, a.rmin, a.rmax);
-            if (stats_m2_applies(c, s, p0)) { em.em_m2 = 1; em.st_col0 = stat_col0(c, s0); }
-        } else if (c->stats_m2) {      // no capacity asked for: nobody reads the spectrum, the last forward step stores nothing
-            em.em_m2 = 2; em.st_col0 = stat_col0(c, s0);
-        }
+        em.em_jp = ph.jit ? tb.jp : nullptr;
+        em.em_med = ph.adaptive ? c->med + 3 * s0 : nullptr; em.em_alpha = (float)a.alpha;
+        em.em_m2 = path.store;
+        if (path.store != STORE_SPEC) em.st_col0 = stat_col0(c, s0);
         // the stream bits in bucket order (the packed frames of the stream pipelines are expanded on the way).  (On the side stream
         // beside the forward transform it gained nothing measurable: 0.03 ms of 3.3.)
         if (walks) HIPCHK(c, launch_gather_bits_walks(tb.ent, a.bits, ep.frame_hdr, ep.frame_pay, ep.frame_plen, n_bits, ep.limit, g, tb.pb + (size_t)s0 * n_bits, st));
-        else HIPCHK(c, launch_gather_bits(tb.ent, tb.off + nb, a.bits, ep.frame_hdr, ep.frame_pay, ep.frame_plen, n_bits, ep.limit, g, tb.pb + (size_t)s0 * n_bits, st));
+        else HIPCHK(c, launch_gather_bits(tb.ent, tb.off + bg.nb, a.bits, ep.frame_hdr, ep.frame_pay, ep.frame_plen, n_bits, ep.limit, g, tb.pb + (size_t)s0 * n_bits, st));
     }
-    if (delta && usable) {
-        // the statistics' bracket pass inside the last forward column step: neither the spectrum nor |F|^2 is stored (unless a plane's
-        // bracket turns out wrong: then the gated plain step produces the spectrum for the fallback kernels)
-        CapParams p = cap_params(c, s, a.rmin, a.rmax);
-        p.magmin = a.magmin;
-        if (tilestats_applies(c, s, plan_cols(c, s.PH, s.PWi, g), p, g)) {
-            em.em_m2 = 0;
-            rc = enqueue_forward_tilestats(c, s0, g, rgb_in, st, em, walks, p, usable, 7);
-            if (rc) return rc;
-            // the select chain is five small dependent launches: on a side stream beside the inverse transform, which does not wait for it
-            hipStream_t sst = st;
-            if (c->stats_async && !adaptive) rc = stats_fork(c, which, st, &sst);
-            if (rc) return rc;
-            rc = enqueue_tilestats_select(c, s0, g, sst);
-            if (rc) return rc;
-            if (adaptive) {         // the embed needs the medians: select, gated re-run and fallbacks all finish before the inverse step
-                rc = enqueue_tilestats_tail(c, s0, g, rgb_in, st, p, usable);
-                if (rc) return rc;
-            }
-            StageMode mi;
-            mi.inv_mode = COLS_EMBED; mi.inv = &em; mi.walks = walks; mi.inv_cover = rgb_in; mi.inv_via_spec = true;
-            rc = enqueue_inverse(c, s0, g, rgb_out, st, mi);
-            if (rc) return rc;
-            if (sst != st) {
-                rc = stats_join(c, which, st);
-                if (rc) return rc;
-            }
-            return adaptive ? TFFT_OK : enqueue_tilestats_tail(c, s0, g, rgb_in, st, p, usable);
-        }
-    }
+    // forward.  In-kernel statistics: the sample, the bracket guess and the COLS_STAT step; neither the spectrum nor |F|^2 is stored (unless
+    // a plane's bracket turns out wrong: then the gated plain step of the tail produces the spectrum for the fallback kernels)
     StageMode md;
-    if (delta) { md.fwd_mode = COLS_EMIT; md.fwd = &em; md.walks = walks; }
-    rc = enqueue_forward(c, s0, g, rgb_in, st, md);
+    if (path.delta) { md.fwd_mode = COLS_EMIT; md.fwd = &em; md.walks = walks; }
+    rc = in_step ? enqueue_forward_tilestats(c, s0, g, rgb_in, st, em, walks, cap, usable, 7) : enqueue_forward(c, s0, g, rgb_in, st, md);
     if (rc) return rc;
-    hipStream_t sst = st;       // the stream the statistics run on
-    const bool async = delta && usable && c->stats_async && !adaptive;      // (adaptive: the embed waits for the medians)
-    if (async) rc = stats_fork(c, which, st, &sst);
-    if (rc) return rc;
-    if (usable) {      // S:922-923, S:998-1012 on the device, no host round trip: capacity is counted inside the median's full pass
-        CapParams p = cap_params(c, s, a.rmin, a.rmax);
-        p.magmin = a.magmin;
-        if (c->stats_fused && p.bw > 0) {
-            rc = enqueue_medians(c, s0, g, sst, &p, usable, em.em_m2 != 0);
-            if (rc) return rc;
-        } else {
+    // the statistics.  With delta embedding nothing downstream reads them unless alpha is adaptive: on a side stream beside the inverse
+    // transform, which does not wait for them (the in-kernel form's select chain is five small dependent launches)
+    hipStream_t sst = st;
+    if (path.side) { rc = stats_fork(c, which, st, &sst); if (rc) return rc; }
+    switch (path.stats) {
+        case STATS_NONE: break;
+        case STATS_IN_STEP:
+            rc = enqueue_tilestats_select(c, s0, g, sst);
+            // adaptive: the embed needs the medians -- select, gated re-run and fallbacks all finish before the inverse step
+            if (!rc && ph.adaptive) rc = enqueue_tilestats_tail(c, s0, g, rgb_in, st, cap, usable);
+            break;
+        case STATS_FUSED:      // S:922-923, S:998-1012 on the device, no host round trip: capacity is counted inside the median's full pass
+            rc = enqueue_medians(c, s0, g, sst, &cap, usable, path.store == STORE_M2);
+            break;
+        case STATS_SEPARATE:
             rc = enqueue_medians(c, s0, g, sst);
             if (rc) return rc;
-            HIPCHK(c, launch_capacity(c->spec(s0), p, g, c->med + 3 * s0, stat_partial(c, s0), usable, sst, nullptr));
-        }
+            HIPCHK(c, launch_capacity(c->spec(s0), cap, g, c->med + 3 * s0, stat_partial(c, s0), usable, sst, nullptr));
+            break;
     }
-    if (delta) {
-        StageMode mi;
-        mi.inv_mode = COLS_EMBED; mi.inv = &em; mi.walks = walks; mi.inv_cover = rgb_in;
-        rc = enqueue_inverse(c, s0, g, rgb_out, st, mi);
-        if (async) {            // whoever waits for the context's stream has the capacities too
-            const int rj = stats_join(c, which, st);
-            if (rj) return rj;
-        }
-        return rc;
+    if (rc) return rc;
+    if (!path.delta) {
+        HIPCHK(c, launch_embed(c->spec(s0), a.bins, a.bits, ph.jit, ep, g, c->err, st));
+        return enqueue_inverse(c, s0, g, rgb_out, st);
     }
-    HIPCHK(c, launch_embed(c->spec(s0), a.bins, a.bits, jit, ep, g, c->err, st));
-    return enqueue_inverse(c, s0, g, rgb_out, st);
+    StageMode mi;
+    mi.inv_mode = COLS_EMBED; mi.inv = &em; mi.walks = walks; mi.inv_cover = rgb_in; mi.inv_via_spec = in_step;
+    rc = enqueue_inverse(c, s0, g, rgb_out, st, mi);
+    if (path.side) {            // (also after a failed inverse.)  Whoever waits for the context's stream has the capacities too
+        const int rj = stats_join(c, which, st);
+        if (rj) return rj;
+    }
+    if (rc || !in_step || ph.adaptive) return rc;
+    return enqueue_tilestats_tail(c, s0, g, rgb_in, st, cap, usable);
 }
 // one chunk of an embed: the images rgb_in (g of them, packed) through slots [s0, s0+g) on stream st -> rgb_out, capacities -> usable (or nullptr)
 static int embed_chunk(tfft_ctx* c, int s0, int g, hipStream_t st, const ChunkArgs& a, const uint8_t* rgb_in, unsigned long long* usable,
                        uint8_t* rgb_out) {
     // adaptive alpha needs every image's medians before the embed: the statistics run whether or not the caller asked for the
     // capacities (these then land in the context's own buffer)
-    if (!usable && (a.per_image ? a.adaptive : c->ph_adaptive != 0) && a.n_bits > 0) usable = c->usable + s0;
+    if (!usable && phase_opts(c, a).adaptive && a.n_bits > 0) usable = c->usable + s0;
     int rc = usable ? stats_clean_if_dirty(c, st) : TFFT_OK;
     if (!rc) rc = embed_chunk_impl(c, s0, g, st, a, rgb_in, usable, rgb_out);
     if (!rc && usable && c->stats_fail_once) {      // test hook (TFFT_STATS_FAIL_ONCE): as if the sequence had broken off -- garbage in the select state, an error out
@@ -1798,62 +1819,55 @@ static int extract_chunk(tfft_ctx* c, int s0, int g, hipStream_t st, const Chunk
     const Slot& s = c->slots[s0];
     const tfft_bin* bins = a.bins;
     const uint64_t n_bits = a.n_bits;
-    const double alpha = a.alpha;
     const bool walks = a.per_image;
     if (!index_ok(c, n_bits) || !phase_ok(c, n_bits)) return TFFT_E_STATE;
-    if (walks && (c->bit_index || c->ph_jit)) return TFFT_E_STATE;
-    const bool adaptive = walks ? a.adaptive : c->ph_adaptive != 0;
-    const float* jit = walks ? a.jit : c->ph_jit;
+    const PhaseOpts ph = phase_opts(c, a);
+    if (ph.rc) return ph.rc;
     // adaptive alpha with |alpha| < pi/2: a = alpha*clamp(.., 0.5, 2) keeps the sign of alpha and |a| < pi, so the targets j +- a are
     // symmetric about j and j + pi and the bit is the side of that line -- what the fixed-alpha read decides.
     // Beyond, the decision depends on the medians: the single-image calls cover that case
-    if (adaptive && !(fabs(alpha) < M_PI / 2)) return TFFT_E_INVALID;
-    const int which = (c->stream2 && st == c->stream2) ? 1 : 0;
-    EmbedParams ep = embed_params(c, s, n_bits, alpha, 0, nullptr, jit != nullptr);
-    if (walks) ep.bins_stride = n_bits;
+    if (ph.adaptive && !(fabs(a.alpha) < M_PI / 2)) return TFFT_E_INVALID;
+    const int which = stream_index(c, st);
+    const bool registered = !walks && bins == c->reg_bins && n_bits == c->reg_n;
+    auto& tb = c->tb[which];
     int rc;
-    // (the bucket build is per call: it pays off from about 8 images per chunk; TFFT_TILE_READ=2/3 force it)
-    // a registered list keeps its buckets (no per-call build to pay for): then the tile-resident read also serves small chunks of LARGE
-    // images (one 4K image: 0.739 -> 0.725 ms per round trip; one 1080p image has too few tiles to fill the chip: 0.265 -> 0.301)
-    const bool reg_large = !walks && bins == c->reg_bins && n_bits == c->reg_n && (unsigned long long)s.PH * s.PWi >= (1ull << 23);
-    // (an alpha outside (0, pi) takes the general phase comparison of k_read: the tile kernel reads the sign of Im only)
-    if (c->tile_read && n_bits > 0 && alpha > 0.0 && alpha < M_PI && (g >= 8 || c->tile_read >= 2 || reg_large)) {
-        // The spectrum is only ever read at the bins of the list: bucket them by column tile and let the final
-        // forward column step read the bits out of its LDS-resident tiles -- no spectrum store, no k_read.
-        const BucketGeom bg = bucket_geom(c, s, g);
-        const int nb = bg.nb;
-        rc = walks ? TFFT_OK : ensure_buckets(c, which, n_bits, nb);
-        if (rc) return rc;
-        auto& tb = c->tb[which];
-        HIPCHK(c, hipMemsetAsync(bits_out, 0, (size_t)g * n_bits, st));          // bins the walk would never produce read as 0 (k_read does the same)
-        rc = walks ? build_buckets_walks(c, which, bins, n_bits, g, s, bg, jit, st) : build_buckets(c, which, bins, n_bits, s, bg.G, st);
-        if (rc) return rc;
-        if (!walks) rc = gather_jitter(c, which, n_bits, nb, st);
-        if (rc) return rc;
-        ColParams rd = bucketed_params(c, which);
-        rd.rd_bits = bits_out; rd.rd_n = n_bits;
-        rd.em_jp = jit ? tb.jp : nullptr;
-        StageMode md;
-        md.fwd_mode = COLS_READ; md.fwd = &rd; md.walks = walks;
-        rc = enqueue_forward(c, s0, g, rgb_in, st, md);
-        if (rc) return rc;
-    } else {
-        // the spectrum is only read at the bins of the list: rows above the highest one are never stored
-        int* last_row = c->last_row + which;
-        auto& tbr = c->tb[which];
-        const bool registered = !walks && bins == c->reg_bins && n_bits == c->reg_n;
-        if (!(registered && tbr.row_for == bins && tbr.row_n == n_bits && tbr.row_ph == s.PH && tbr.row_pw == s.PWi)) {
-            // (one walk per image: the highest row over all the chunk's lists)
-            HIPCHK(c, launch_bins_last_row(bins, walks ? (uint64_t)g * n_bits : n_bits, s.PH, s.PWi, last_row, st));
-            tbr.row_for = registered ? bins : nullptr; tbr.row_n = n_bits; tbr.row_ph = s.PH; tbr.row_pw = s.PWi;
+    switch (read_form(c, s, g, a, registered)) {
+        case READ_TILES: {
+            const BucketGeom bg = bucket_geom(c, s, g);
+            rc = walks ? TFFT_OK : ensure_buckets(c, which, n_bits, bg.nb);
+            if (rc) return rc;
+            HIPCHK(c, hipMemsetAsync(bits_out, 0, (size_t)g * n_bits, st));          // bins the walk would never produce read as 0 (k_read does the same)
+            rc = walks ? build_buckets_walks(c, which, bins, n_bits, g, s, bg, ph.jit, st) : build_buckets(c, which, bins, n_bits, s, bg.G, st);
+            if (rc) return rc;
+            if (!walks) rc = gather_jitter(c, which, n_bits, bg.nb, st);
+            if (rc) return rc;
+            ColParams rd = bucketed_params(c, which);
+            rd.rd_bits = bits_out; rd.rd_n = n_bits;
+            rd.em_jp = ph.jit ? tb.jp : nullptr;
+            StageMode md;
+            md.fwd_mode = COLS_READ; md.fwd = &rd; md.walks = walks;
+            rc = enqueue_forward(c, s0, g, rgb_in, st, md);
+            if (rc) return rc;
+            break;
         }
-        ColParams rl{};
-        rl.last_row_dev = last_row;
-        StageMode md;
-        md.fwd_mode = COLS_ROWLIMIT; md.fwd = &rl;
-        rc = enqueue_forward(c, s0, g, rgb_in, st, md);
-        if (rc) return rc;
-        HIPCHK(c, launch_read(c->spec(s0), bins, jit, ep, g, bits_out, c->err, st));
+        case READ_ROWLIMIT: {
+            int* last_row = c->last_row + which;
+            if (!(registered && tb.row_for == bins && tb.row_n == n_bits && tb.row_ph == s.PH && tb.row_pw == s.PWi)) {
+                // (one walk per image: the highest row over all the chunk's lists)
+                HIPCHK(c, launch_bins_last_row(bins, walks ? (uint64_t)g * n_bits : n_bits, s.PH, s.PWi, last_row, st));
+                tb.row_for = registered ? bins : nullptr; tb.row_n = n_bits; tb.row_ph = s.PH; tb.row_pw = s.PWi;
+            }
+            ColParams rl{};
+            rl.last_row_dev = last_row;
+            StageMode md;
+            md.fwd_mode = COLS_ROWLIMIT; md.fwd = &rl;
+            rc = enqueue_forward(c, s0, g, rgb_in, st, md);
+            if (rc) return rc;
+            EmbedParams ep = embed_params(c, s, n_bits, a.alpha, 0, nullptr, ph.jit != nullptr);
+            if (walks) ep.bins_stride = n_bits;
+            HIPCHK(c, launch_read(c->spec(s0), bins, ph.jit, ep, g, bits_out, c->err, st));
+            break;
+        }
     }
     for (int i = 0; i < g; i++) c->slots[s0 + i].has_spec = false;      // partial or no spectrum: not for tfft_medians & co
     return TFFT_OK;
@@ -2325,7 +2339,7 @@ static int fit_chunk(tfft_ctx* c, int g, const ChunkArgs& a, const uint8_t* cove
     rc = check_err_flag(c);         // (a bin out of range: the buckets do not describe the lists)
     if (rc) return rc;
     auto& tb = c->tb[0];
-    if (!c->embed_delta) {          // TFFT_EMBED_DELTA=0 wrote F' into the spectrum: no buckets, no F0 in bucket order yet
+    if (!embed_path(c, s, g, a, usable != nullptr).delta) {      // (TFFT_EMBED_DELTA=0) F' was written into the spectrum: no buckets, no F0 in bucket order yet
         const BucketGeom bg = bucket_geom(c, s, g);
         rc = ensure_buckets(c, 0, n_bins, bg.nb, true);
         if (!rc) rc = build_buckets_walks(c, 0, bins, n_bins, g, s, bg, jit, st);
@@ -2664,50 +2678,49 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
     if ((stage == COLS_FWD_B || stage == COLS_INV_B) && pl.direct) launches = 0;
     if ((stage == COLS_FWD_A || stage == COLS_INV_B) && pl.fused_fwd) launches = 0;
     if (stage == ROWS_FWD && pl.fused_fwd && c->fuse_live && s.H < s.PH && (s.H % (s.PH >> 3)) != 0) launches = 2;      // one per live-row count
-    if (stage == CAPACITY) launches = c->stats_fused ? 0 : 2;      // fused: counted inside the medians' full pass
-    // delta embedding (see embed_chunk): the batched pipeline has no k_embed launch, its first inverse step builds the tiles from the
-    // bins and its row kernel adds the cover -- the stages are timed the way the pipeline runs them
-    bool delta = false;
-    if (c->embed_delta && bins_dev && n_bits > 0 && (stage == EMBED || stage == COLS_INV_A || stage == ROWS_INV || stage == final_fwd || stage == MEDIANS)) {
-        const EmbedParams ep0 = embed_params(c, s, n_bits, alpha, 0, nullptr, false);
-        delta = !ep0.generic;
-    }
-    CapParams tcap = cap_params(c, s, 0.05, 0.45);
-    tcap.magmin = 0.01;
-    // the statistics inside the last forward column step (see embed_chunk): that step is timed as COLS_STAT; MEDIANS is everything else
-    // of the statistics -- sample pass + bracket guess before it, select chain, gated step, fallback and capacity kernels after it
-    const bool tile = delta && bits_dev && tilestats_applies(c, s, pl, tcap, n_images) && (stage == final_fwd || stage == MEDIANS);
-    const bool m2 = delta && bits_dev && !tile && stats_m2_applies(c, s, tcap);      // the spectrum is stored as |F|^2 + column 0 (see embed_chunk)
+    // The stages are timed the way the pipelines run a chunk of n_images covers with the shared list bins_dev, plain bits and the default
+    // capacities: embed_path and read_form say which way that is.  (Delta embedding: no k_embed launch, the first inverse step builds the tiles
+    // from the bins and the row kernel adds the cover.  Without bins or bits there is nothing to embed: the stages of the write-F' path)
+    const ChunkArgs a = ChunkArgs::list(bins_dev, n_bits, alpha).capacity(0.05, 0.45, 0.01).plain(bits_dev);
+    ChunkArgs ae = a;
+    if (!bins_dev || !bits_dev) ae.n_bits = 0;
+    const EmbedPath path = embed_path(c, s, n_images, ae, true);
+    CapParams tcap = cap_params(c, s, a.rmin, a.rmax);
+    tcap.magmin = a.magmin;
+    // the statistics inside the last forward column step: that step is timed as COLS_STAT; MEDIANS is everything else of the
+    // statistics -- sample pass + bracket guess before it, select chain, gated step, fallback and capacity kernels after it
+    const bool tile = path.stats == STATS_IN_STEP && (stage == final_fwd || stage == MEDIANS);
+    if (stage == CAPACITY) launches = path.stats == STATS_SEPARATE ? 2 : 0;      // else counted inside the medians' full pass
     if (stage == MEDIANS) {
         // tile: the sample pass and the gated plain step (FFT stages) + the statistics' own kernels around the COLS_STAT step
         if (tile) launches = 2 + stat_tile_launches(stat_opts(c, &tcap, false));
-        else launches = plan_medians(s.PH, s.PWi, n_images, stat_opts(c, c->stats_fused ? &tcap : nullptr, m2)).launches;
+        else launches = plan_medians(s.PH, s.PWi, n_images, stat_opts(c, path.stats == STATS_FUSED ? &tcap : nullptr, path.store == STORE_M2)).launches;
     }
-
     if (n_launches) *n_launches = launches;
     *ms_per_rep = 0.f;
     if (launches == 0) return TFFT_OK;
     const BucketGeom bg = bucket_geom(c, s, n_images);      // (as embed_chunk and extract_chunk bucket the list)
     { const float2* t; int rc = get_twiddles(c, s.PWi, &t); if (rc) return rc; rc = get_twiddles(c, s.PH, &t); if (rc) return rc; }
     ColParams rd{};
-    bool tile_read = false;      // COLS_FWD_READ: the tile-resident read (else the row-limited step)
+    // COLS_FWD_READ: the last forward step of an extract of a list that is NOT registered, whatever the context has registered (a registered
+    // list would move small chunks of large images to the tile-resident read: the stage table keeps the per-call form)
+    const bool tile_read = stage == COLS_FWD_READ && read_form(c, s, n_images, a, false) == READ_TILES;
     if (stage == COLS_FWD_READ) {
         if (!bins_dev || !index_ok(c, n_bits)) return TFFT_E_INVALID;
-        if (c->tile_read && n_bits > 0 && (n_images >= 8 || c->tile_read >= 2)) {
+        if (tile_read) {
             if (!bits_out_dev) return TFFT_E_INVALID;
             int rc = ensure_buckets(c, 0, n_bits, bg.nb);
+            if (!rc) rc = build_buckets(c, 0, (const tfft_bin*)bins_dev, n_bits, s, bg.G, c->stream);
             if (rc) return rc;
-            HIPCHK(c, launch_bucket_bins((const tfft_bin*)bins_dev, c->bit_index, n_bits, s.PH, s.PWi, bg.G, c->tb[0].cnt, c->tb[0].off, c->tb[0].ent, c->err, c->tile_read == 2, c->stream));
             rd = bucketed_params(c, 0);
             rd.rd_bits = (uint8_t*)bits_out_dev; rd.rd_n = n_bits;
-            tile_read = true;
         } else {
             HIPCHK(c, launch_bins_last_row((const tfft_bin*)bins_dev, n_bits, s.PH, s.PWi, c->last_row, c->stream));
             rd.last_row_dev = c->last_row;
         }
     }
     ColParams em{};
-    const bool delta_lists = (stage == COLS_INV_A || stage == final_fwd || stage == EMBED || (stage == MEDIANS && tile)) && delta && bits_dev;
+    const bool delta_lists = (stage == COLS_INV_A || stage == final_fwd || stage == EMBED || (stage == MEDIANS && tile)) && path.delta;
     if (delta_lists) {
         if (!index_ok(c, n_bits)) return TFFT_E_STATE;
         int rc = ensure_buckets(c, 0, n_bits, bg.nb, true);
@@ -2718,83 +2731,69 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
         em = bucketed_params(c, 0);
         em.em_fl = c->tb[0].fl; em.em_pb = c->tb[0].pb; em.em_n = n_bits;
         em.em_cos = ep0.cos_a; em.em_sin = ep0.sin_a;
-        if (m2) { em.em_m2 = 1; em.st_col0 = c->col0_pool; }
+        em.em_m2 = path.store;
+        if (path.store != STORE_SPEC) em.st_col0 = c->col0_pool;
     }
+    // reps back-to-back runs of body() between two events on the context's stream
+    auto timed = [&](auto&& body, float* ms) -> int {
+        HIPCHK(c, hipEventRecord(c->ev_t0, c->stream));
+        for (int r = 0; r < reps; r++) { const int rc = body(); if (rc) return rc; }
+        HIPCHK(c, hipEventRecord(c->ev_t1, c->stream));
+        HIPCHK(c, hipEventSynchronize(c->ev_t1));
+        HIPCHK(c, hipEventElapsedTime(ms, c->ev_t0, c->ev_t1));
+        return TFFT_OK;
+    };
     if (tile) {
         // phases of enqueue_forward_tilestats: 2 sample + guess, 4 COLS_STAT, 8 select, 16 tail.  The COLS_STAT step alone needs a bracket
         // (one untimed sample pass); MEDIANS = the whole sequence minus the COLS_STAT launches it contains, timed the same way
         float ms_all = 0.f, ms_stat = 0.f;
-        int rc = enqueue_forward_tilestats(c, 0, n_images, (const uint8_t*)rgb_dev, c->stream, em, false, tcap, c->usable, 2);
+        auto run = [&](int phases) { return enqueue_forward_tilestats(c, 0, n_images, (const uint8_t*)rgb_dev, c->stream, em, false, tcap, c->usable, phases); };
+        int rc = run(2);
+        if (!rc) rc = timed([&] { return run(4); }, &ms_stat);
+        if (!rc && stage == MEDIANS) rc = timed([&] { return run(2 | 4 | 8 | 16); }, &ms_all);
         if (rc) return rc;
-        HIPCHK(c, hipEventRecord(c->ev_t0, c->stream));
-        for (int r = 0; r < reps; r++) { rc = enqueue_forward_tilestats(c, 0, n_images, (const uint8_t*)rgb_dev, c->stream, em, false, tcap, c->usable, 4); if (rc) return rc; }
-        HIPCHK(c, hipEventRecord(c->ev_t1, c->stream));
-        HIPCHK(c, hipEventSynchronize(c->ev_t1));
-        HIPCHK(c, hipEventElapsedTime(&ms_stat, c->ev_t0, c->ev_t1));
-        if (stage == MEDIANS) {
-            HIPCHK(c, hipEventRecord(c->ev_t0, c->stream));
-            for (int r = 0; r < reps; r++) { rc = enqueue_forward_tilestats(c, 0, n_images, (const uint8_t*)rgb_dev, c->stream, em, false, tcap, c->usable, 2 | 4 | 8 | 16); if (rc) return rc; }
-            HIPCHK(c, hipEventRecord(c->ev_t1, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev_t1));
-            HIPCHK(c, hipEventElapsedTime(&ms_all, c->ev_t0, c->ev_t1));
-        }
         *ms_per_rep = (stage == MEDIANS ? (ms_all > ms_stat ? ms_all - ms_stat : 0.f) : ms_stat) / (float)reps;
         return TFFT_OK;
     }
-    HIPCHK(c, hipEventRecord(c->ev_t0, c->stream));
-    for (int r = 0; r < reps; r++) {
-        int rc = TFFT_OK;
+    auto fft_stage = [&](int stg, const StageMode& md) { return enqueue_fft_stage(c, 0, n_images, stg, (const uint8_t*)rgb_dev, (uint8_t*)rgb_out_dev, c->stream, md); };
+    float ms = 0.f;
+    const int rc = timed([&]() -> int {
+        StageMode md;
         switch (stage) {
             case COLS_FWD_A:
             case COLS_FWD_B:
-                { StageMode md; if (delta_lists && stage == final_fwd) { md.fwd_mode = COLS_EMIT; md.fwd = &em; }
-                  rc = enqueue_fft_stage(c, 0, n_images, stage, (const uint8_t*)rgb_dev, nullptr, c->stream, md); }
-                break;
+                if (delta_lists && stage == final_fwd) { md.fwd_mode = COLS_EMIT; md.fwd = &em; }
+                return fft_stage(stage, md);
             case COLS_INV_A:
-                { StageMode md; if (delta_lists) { md.inv_mode = COLS_EMBED; md.inv = &em; }
-                  rc = enqueue_fft_stage(c, 0, n_images, stage, nullptr, nullptr, c->stream, md); }
-                break;
+                if (delta_lists) { md.inv_mode = COLS_EMBED; md.inv = &em; }
+                return fft_stage(stage, md);
             case ROWS_INV:
-                { StageMode md; if (delta && rgb_dev) md.inv_cover = (const uint8_t*)rgb_dev;
-                  rc = enqueue_fft_stage(c, 0, n_images, stage, nullptr, (uint8_t*)rgb_out_dev, c->stream, md); }
-                break;
+                if (path.delta && rgb_dev) md.inv_cover = (const uint8_t*)rgb_dev;
+                return fft_stage(stage, md);
             case COLS_FWD_READ:
-                { StageMode md; md.fwd_mode = tile_read ? COLS_READ : COLS_ROWLIMIT; md.fwd = &rd;
-                  rc = enqueue_fft_stage(c, 0, n_images, final_fwd, nullptr, nullptr, c->stream, md); }
-                break;
-            case EMBED: {
+                md.fwd_mode = tile_read ? COLS_READ : COLS_ROWLIMIT; md.fwd = &rd;
+                return fft_stage(final_fwd, md);
+            case EMBED:
                 if (!index_ok(c, n_bits)) return TFFT_E_STATE;
-                if (delta_lists) {      // delta embedding: what is left of the embed stage is the gather of the stream bits into bucket order
-                    HIPCHK(c, launch_gather_bits(c->tb[0].ent, c->tb[0].off + bg.nb, (const uint8_t*)bits_dev, nullptr, nullptr, 0, n_bits, n_bits, n_images, c->tb[0].pb, c->stream));
-                    break;
-                }
-                EmbedParams ep = embed_params(c, s, n_bits, alpha, 0, nullptr, false);
-                HIPCHK(c, launch_embed(c->spec(0), (const tfft_bin*)bins_dev, (const uint8_t*)bits_dev, nullptr, ep, n_images, c->err, c->stream));
-                break;
-            }
-            case READ: {
+                // delta embedding: what is left of the embed stage is the gather of the stream bits into bucket order
+                if (delta_lists) HIPCHK(c, launch_gather_bits(c->tb[0].ent, c->tb[0].off + bg.nb, (const uint8_t*)bits_dev, nullptr, nullptr, 0, n_bits, n_bits, n_images, c->tb[0].pb, c->stream));
+                else HIPCHK(c, launch_embed(c->spec(0), (const tfft_bin*)bins_dev, (const uint8_t*)bits_dev, nullptr, embed_params(c, s, n_bits, alpha, 0, nullptr, false), n_images, c->err, c->stream));
+                return TFFT_OK;
+            case READ:
                 if (!index_ok(c, n_bits)) return TFFT_E_STATE;
-                EmbedParams ep = embed_params(c, s, n_bits, alpha, 0, nullptr, false);
-                HIPCHK(c, launch_read(c->spec(0), (const tfft_bin*)bins_dev, nullptr, ep, n_images, (uint8_t*)bits_out_dev, c->err, c->stream));
-                break;
-            }
+                HIPCHK(c, launch_read(c->spec(0), (const tfft_bin*)bins_dev, nullptr, embed_params(c, s, n_bits, alpha, 0, nullptr, false), n_images, (uint8_t*)bits_out_dev, c->err, c->stream));
+                return TFFT_OK;
             case MEDIANS:
-                if (c->stats_fused) rc = enqueue_medians(c, 0, n_images, c->stream, &tcap, c->usable, m2);
-                else rc = enqueue_medians(c, 0, n_images, c->stream);
-                break;
+                if (path.stats == STATS_FUSED) return enqueue_medians(c, 0, n_images, c->stream, &tcap, c->usable, path.store == STORE_M2);
+                return enqueue_medians(c, 0, n_images, c->stream);
             case CAPACITY:
                 HIPCHK(c, launch_capacity(c->spec(0), tcap, n_images, c->med, c->partial, c->usable, c->stream, nullptr));
-                break;
-            default: rc = enqueue_fft_stage(c, 0, n_images, stage, (const uint8_t*)rgb_dev, (uint8_t*)rgb_out_dev, c->stream);
+                return TFFT_OK;
+            default: return fft_stage(stage, md);
         }
-        if (rc) return rc;
-    }
-    HIPCHK(c, hipEventRecord(c->ev_t1, c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev_t1));
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_t0, c->ev_t1));
+    }, &ms);
     *ms_per_rep = ms / (float)reps;
-    return TFFT_OK;
+    return rc;
 }
 
 // ---------------------------------------------------------------- (f-4) fp64 audit transform
