@@ -339,6 +339,54 @@ int tfft_quality_batch_dev(tfft_ctx* ctx, int n_images, const void* a_dev, const
 int tfft_quality_batch(tfft_ctx* ctx, int n_images, const uint8_t* a, const uint8_t* b, int w, int h,
                        uint64_t* sse_out, double* ssim_out /* or NULL */);
 
+/* ------------------------------------------------------------ robustness analysis
+ * How much noise or recompression a stego batch survives, measured on the device: a channel attacks the images, the stream extractor reads them,
+ * and the errors are counted against what was embedded (the "BER vs AWGN/JPEG" tests of the reference's roadmap).
+ * A channel: kind 0 none (a copy); kind 1 AWGN, param = sigma in grey levels (>= 0, finite), seed used; kind 2 JPEG quantisation, param =
+ * quality, an integer 1..100.  Images are packed RGB8, image i at + i*w*h*3; rgb_out may be rgb (in place).  first_image is the index of
+ * image 0 in the caller's numbering: the bytes do not depend on how a batch is cut into calls, and repeated calls return identical bytes.
+ *   AWGN, for image i (counted from first_image) and byte p = (y*w + x)*3 + c:  k = seed + 0x9E3779B97F4A7C15 * (i*w*h*3 + p) mod 2^64,
+ *        z = splitmix64(k), u1 = ((z >> 40) + 0.5) / 2^24, u2 = (((z >> 16) & 0xFFFFFF) + 0.5) / 2^24, g = sqrt(-2 ln u1) cos(2 pi u2),
+ *        out = clamp(rint(pixel + sigma*g), 0, 255), evaluated in fp32 (within 1e-4 max(1, sigma) of the fp64 value before rounding).
+ *   JPEG quantisation: the lossy part of baseline JPEG, not its file format.  JFIF full-range BT.601 to Y - 128, Cb, Cr in floating point;
+ *        4:4:4; 8 x 8 blocks from (0, 0), the right and bottom edge blocks completed by repeating the last column / row; orthonormal 2-D
+ *        DCT-II; the Annex K luminance table for Y and chrominance table for Cb / Cr in natural order, scaled the IJG way (s = 5000 div Q for
+ *        Q < 50, else 200 - 2Q; q = clamp((base*s + 50) div 100, 1, 255)); level = rint(c/q), c' = level*q; inverse DCT, Y + 128, inverse colour
+ *        transform, clamp(rint(.), 0, 255).  Only the w x h pixels are written.
+ *        Left out: chroma subsampling, the decoder's rounding of YCbCr to 8 bits, and entropy coding (lossless).  None changes the error
+ *        mechanism that matters to a phase embedding, which is the quantisation of the coefficients.
+ * Invalid kind, sigma < 0 or not finite, quality outside 1..100 or not an integer: TFFT_E_INVALID; w > max_w or h > max_h: TFFT_E_TOO_LARGE.
+ * The calls leave the slots alone (like tfft_quality_batch).  The _dev form does not synchronise; the host form stages one chunk of n_slots
+ * images at a time in the analysis scratch and synchronises. */
+typedef struct tfft_channel { int32_t kind; float param; uint64_t seed; } tfft_channel;
+int tfft_channel_batch_dev(tfft_ctx* ctx, int n_images, const void* rgb_dev, int w, int h, const tfft_channel* ch /* host */,
+                           uint64_t first_image, void* rgb_out_dev);
+int tfft_channel_batch(tfft_ctx* ctx, int n_images, const uint8_t* rgb, int w, int h, const tfft_channel* ch, uint64_t first_image,
+                       uint8_t* rgb_out);
+/* For every channel k and image i, result[(k*n_images + i)*4 ..] = {raw_bit_errors, header_byte_errors, payload_byte_errors, (uint32)status}
+ * of the stego images read back after channel k, exactly as this sequence of calls on the same context gives them:
+ *   1. tfft_channel_batch_dev(stego, channels[k], first_image) -> the attacked batch;
+ *   2. tfft_extract_stream_batch_dev(attacked, bins, n_bins, alpha, ..., max_payload_len = payload_len, raw_bits_out) -> raw bits and status
+ *      (clen, or -1 / -2 / -3); it honours the bit index, the registered list and tfft_set_phase_options as that call does;
+ *   3. raw_bit_errors = Hamming distance of the first 912 + 56*payload_len raw bits to tfft_frame_expand_dev(header, payload, payload_len);
+ *   4. header_byte_errors / payload_byte_errors = bytes of tfft_frame_majority_dev(raw bits, payload_len) that differ from the given header
+ *      (38 bytes per image) and payload (payload_len bytes per image): a decode at the KNOWN length, so the error rate after the
+ *      repetition code stays measurable when the header is lost.
+ * n_bins >= 912 + 56*payload_len and n_channels >= 1, else TFFT_E_INVALID; otherwise the errors of the calls above.  Works chunk by chunk
+ * (n_slots images, every channel in turn) and keeps one attacked copy of a chunk in a scratch buffer grown on demand; stego_dev is never
+ * written.  Results do not depend on n_slots, and repeated calls return the same.  The slots are left as by an extract batch call.  The _dev
+ * form does not synchronise (but for growing its scratch); the host form stages chunk by chunk like tfft_phase_hist_batch and synchronises.
+ * One list for all images: there is no _walks form. */
+int tfft_robustness_batch_dev(tfft_ctx* ctx, int n_images, const void* stego_dev, int w, int h, int center,
+                              const void* bins_dev, uint64_t n_bins, double alpha,
+                              const void* header_dev, const void* payload_dev, uint64_t payload_len,
+                              const tfft_channel* channels /* host */, int n_channels, uint64_t first_image,
+                              void* result_out_dev /* uint32 [n_channels][n_images][4] */);
+int tfft_robustness_batch(tfft_ctx* ctx, int n_images, const uint8_t* stego, int w, int h, int center,
+                          const tfft_bin* bins, uint64_t n_bins, double alpha,
+                          const uint8_t* header, const uint8_t* payload, uint64_t payload_len,
+                          const tfft_channel* channels, int n_channels, uint64_t first_image, uint32_t* result_out);
+
 /* --------------------------------------------------------- keyed walk (HOST)
  * KS + Turtle + the density gate (S:665-695, S:749-810, S:1076-1081): a
  * resumable generator of embedding positions.  Pure host code, no device.

@@ -6,6 +6,8 @@ The histograms come from ``Context.phase_hist_batch_*`` (tfft_phase_hist_batch[_
   kl_divergence KL(P || Q) of two count histograms, add-half smoothed: P = (c + 0.5) / (N + 0.5 nb), natural log
   peak_mass     the share of a histogram in the bins that hold +alpha and -alpha (the phase-histogram detector's peak statistic)
   auc           the Mann-Whitney statistic: P(pos > neg) + P(pos == neg) / 2
+and from the counts of ``Context.robustness_batch_*`` (tfft_robustness_batch[_dev]):
+  raw_ber, byte_error_rate, recovered   raw bit error rate, byte error rate after the repetition code, and whether the message came back
 """
 import numpy as np
 
@@ -47,6 +49,26 @@ def peak_mass(hist, alpha, half_width_bins=0):
     tot = h.sum(axis=-1)
     sel = h[..., peak_bins(h.shape[-1], alpha, half_width_bins)].sum(axis=-1)
     return np.where(tot > 0, sel / np.where(tot > 0, tot, 1.0), 0.0)
+
+
+# ---- robustness: figures from the (n_channels, n_images, 4) uint32 result of Context.robustness_batch_*
+def raw_ber(result, payload_len):
+    """raw bit error rate per (channel, image): raw_bit_errors / (912 + 56 payload_len)"""
+    r = np.asarray(result)
+    return r[..., 0].astype(np.float64) / float(912 + 56 * int(payload_len))
+
+
+def byte_error_rate(result, payload_len):
+    """byte error rate after the repetition code, decoded at the known length: (header + payload byte errors) / (38 + payload_len)"""
+    r = np.asarray(result)
+    return (r[..., 1].astype(np.float64) + r[..., 2].astype(np.float64)) / float(38 + int(payload_len))
+
+
+def recovered(result, payload_len):
+    """True where the message came back: no header or payload byte differs and the extractor's status is the length the header
+    announces, payload_len - 16"""
+    r = np.asarray(result)
+    return (r[..., 1] == 0) & (r[..., 2] == 0) & (r[..., 3].astype(np.int64) == int(payload_len) - 16)
 
 
 def auc(pos_scores, neg_scores):

@@ -89,6 +89,10 @@ SYMBOLS = {
     "tfft_phase_hist_batch": (_i, [_vp, _i, _vp, _i, _i, _i, _d, _d, _vp, _i, _vp]),
     "tfft_quality_batch_dev": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "tfft_quality_batch": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "tfft_channel_batch_dev": (_i, [_vp, _i, _vp, _i, _i, _vp, _u64, _vp]),
+    "tfft_channel_batch": (_i, [_vp, _i, _vp, _i, _i, _vp, _u64, _vp]),
+    "tfft_robustness_batch_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _u64, _d, _vp, _vp, _u64, _vp, _i, _u64, _vp]),
+    "tfft_robustness_batch": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _u64, _d, _vp, _vp, _u64, _vp, _i, _u64, _vp]),
     "tfft_profile_stage": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _u64, _d, C.POINTER(C.c_float), _pi]),
     "tfft_timer_begin": (_i, [_vp]),
     "tfft_timer_end": (_i, [_vp, C.POINTER(C.c_float)]),
@@ -132,6 +136,25 @@ def _ptr(a):
     if isinstance(a, int):
         return C.c_void_p(a)
     return a.ctypes.data_as(C.c_void_p)
+
+
+# numpy view of struct tfft_channel {int32 kind; float param; uint64 seed;}
+CHANNEL_DTYPE = np.dtype([("kind", "<i4"), ("param", "<f4"), ("seed", "<u8")])
+assert CHANNEL_DTYPE.itemsize == 16
+CHANNEL_NONE, CHANNEL_AWGN, CHANNEL_JPEG = 0, 1, 2
+
+
+def make_channels(specs):
+    """("none",) / ("awgn", sigma[, seed]) / ("jpeg", quality) tuples (or ready records) -> tfft_channel records"""
+    if isinstance(specs, np.ndarray) and specs.dtype == CHANNEL_DTYPE:
+        return np.ascontiguousarray(specs)
+    kinds = {"none": CHANNEL_NONE, "awgn": CHANNEL_AWGN, "jpeg": CHANNEL_JPEG}
+    out = np.zeros(len(specs), CHANNEL_DTYPE)
+    for i, s in enumerate(specs):
+        out[i]["kind"] = kinds[s[0]]
+        out[i]["param"] = s[1] if len(s) > 1 else 0.0
+        out[i]["seed"] = s[2] if len(s) > 2 else 0
+    return out
 
 
 def make_bins(triples):
@@ -494,6 +517,45 @@ class Context:
         out = np.zeros((n, 3), np.float64) if ssim else None
         _check(self.lib.tfft_quality_batch(self.h, n, _ptr(a), _ptr(b), w, h, _ptr(sse), _ptr(out)), "tfft_quality_batch")
         return sse, out
+
+    # ---- robustness analysis -----------------------------------------------------------------
+    def channel_batch_dev(self, n_images, rgb_ptr, w, h, channel, out_ptr, first_image=0):
+        """one channel (a make_channels spec) over n packed images (device); out_ptr may be rgb_ptr"""
+        ch = make_channels([channel] if isinstance(channel, tuple) else channel)
+        _check(self.lib.tfft_channel_batch_dev(self.h, n_images, _ptr(rgb_ptr), w, h, _ptr(ch), first_image, _ptr(out_ptr)),
+               "tfft_channel_batch_dev")
+
+    def channel_batch_host(self, rgb, channel, first_image=0, out=None):
+        """rgb: (n,H,W,3) uint8 host array -> the attacked images (out: written and returned; may be rgb)"""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        n, h, w = rgb.shape[:3]
+        out = np.zeros_like(rgb) if out is None else out
+        ch = make_channels([channel] if isinstance(channel, tuple) else channel)
+        _check(self.lib.tfft_channel_batch(self.h, n, _ptr(rgb), w, h, _ptr(ch), first_image, _ptr(out)), "tfft_channel_batch")
+        return out
+
+    def robustness_batch_dev(self, n_images, stego_ptr, w, h, bins_ptr, n_bins, header_ptr, payload_ptr, payload_len, channels, result_ptr,
+                             alpha=0.5, center=False, first_image=0):
+        """result (device): uint32 [n_channels][n_images][4] = raw bit errors, header byte errors, payload byte errors, status"""
+        ch = make_channels(channels)
+        _check(self.lib.tfft_robustness_batch_dev(self.h, n_images, _ptr(stego_ptr), w, h, int(center), _ptr(bins_ptr), n_bins, alpha,
+                                                  _ptr(header_ptr), _ptr(payload_ptr), payload_len, _ptr(ch), len(ch), first_image,
+                                                  _ptr(result_ptr)), "tfft_robustness_batch_dev")
+
+    def robustness_batch_host(self, stego, bins, header, payload, channels, alpha=0.5, center=False, first_image=0):
+        """stego: (n,H,W,3) uint8; bins: BIN_DTYPE list shared by the images; header (n,38), payload (n,L) uint8
+        -> (n_channels, n, 4) uint32"""
+        stego = np.ascontiguousarray(stego, np.uint8)
+        n, h, w = stego.shape[:3]
+        bins = np.ascontiguousarray(bins, BIN_DTYPE)
+        header = np.ascontiguousarray(header, np.uint8)
+        payload = np.ascontiguousarray(payload, np.uint8)
+        ch = make_channels(channels)
+        out = np.zeros((len(ch), n, 4), np.uint32)
+        _check(self.lib.tfft_robustness_batch(self.h, n, _ptr(stego), w, h, int(center), _ptr(bins), len(bins), alpha, _ptr(header),
+                                              _ptr(payload), payload.shape[1], _ptr(ch), len(ch), first_image, _ptr(out)),
+               "tfft_robustness_batch")
+        return out
 
     STAGES = ["rows_fwd", "cols_fwd_a", "cols_fwd_b", "embed", "cols_inv_a", "cols_inv_b", "rows_inv", "read",
               "medians", "capacity", "cols_fwd_read"]

@@ -11,7 +11,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <array>
+#include <cmath>
 #include <random>
 #include <stdexcept>
 #include <string>
@@ -37,6 +39,9 @@ struct Params {     // S:375-381
 };
 struct Args {       // S:839-845
     std::string mode, inPath, outPath, secret, pass, keyBase64, keyOutPath, wrapPass;
+    std::string robust;             // embed only, not in the reference: --robust SPEC, the channels the written stego is tested against
+    std::vector<tfft_channel> channels;      // ... parsed, and each channel's own text
+    std::vector<std::string> channel_names;
     Params P;
 };
 
@@ -51,6 +56,8 @@ void usage() {
             "      [--pbkdf2_iter 600000 --adaptive_alpha 0 --cover_dependent_path 0 --wrap-pass PW]\n"
             "      [--fit_crop 0]  1: fit the stego so that covers whose sides are not powers of two read back\n"
             "      [--report 0]    1: print PSNR, SSIM and the annulus phase-histogram KL(stego||cover) per plane on stderr\n"
+            "      [--robust SPEC] read the written stego back through channels and print the error counts on stderr;\n"
+            "                      SPEC = comma list of none | awgn:SIGMA[:SEED] | jpeg:Q   (e.g. none,awgn:2:7,jpeg:75)\n"
             "  turtlefft extract --in stego.png (--pass PW | --key KEY_BASE64)\n"
             "      [same tuning options as embed]\n"
             "  The 2-D FFT / phase embedding runs on an AMD MI355X through libturtlefft_hip.so.\n");
@@ -75,6 +82,7 @@ const OptSpec kOptions[] = {
     {"--key", OptKind::Text, &Args::keyBase64, nullptr, nullptr, nullptr},
     {"--key-out", OptKind::Text, &Args::keyOutPath, nullptr, nullptr, nullptr},
     {"--wrap-pass", OptKind::Text, &Args::wrapPass, nullptr, nullptr, nullptr},
+    {"--robust", OptKind::Text, &Args::robust, nullptr, nullptr, nullptr},
     {"--alpha", OptKind::Real, nullptr, &Params::alpha, nullptr, nullptr},
     {"--jitter", OptKind::Real, nullptr, &Params::jitter, nullptr, nullptr},
     {"--density", OptKind::Real, nullptr, &Params::density, nullptr, nullptr},
@@ -95,6 +103,42 @@ const OptSpec* find_option(const char* name) {
     return nullptr;
 }
 
+// --robust SPEC: a comma list of none | awgn:SIGMA[:SEED] | jpeg:Q.  Anything else (an empty item, an unknown channel, a number with a tail,
+// sigma < 0, Q outside 1..100) is a usage error
+bool parse_number(const std::string& t, double& v) {
+    if (t.empty()) return false;
+    char* end = nullptr;
+    v = strtod(t.c_str(), &end);
+    return end && *end == '\0' && std::isfinite(v);
+}
+bool parse_channels(const std::string& spec, std::vector<tfft_channel>& out, std::vector<std::string>& names) {
+    size_t pos = 0;
+    while (pos <= spec.size()) {
+        const size_t comma = std::min(spec.find(',', pos), spec.size());
+        const std::string item = spec.substr(pos, comma - pos);
+        pos = comma + 1;
+        std::vector<std::string> f;
+        for (size_t a = 0; a <= item.size();) { const size_t c = std::min(item.find(':', a), item.size()); f.push_back(item.substr(a, c - a)); a = c + 1; }
+        tfft_channel ch{0, 0.0f, 0};
+        double v = 0.0;
+        if (f[0] == "none" && f.size() == 1) ch.kind = 0;
+        else if (f[0] == "awgn" && (f.size() == 2 || f.size() == 3)) {
+            if (!parse_number(f[1], v) || v < 0.0) return false;
+            ch.kind = 1; ch.param = (float)v;
+            if (f.size() == 3) {
+                if (f[2].empty() || f[2].find_first_not_of("0123456789") != std::string::npos || f[2].size() > 19) return false;
+                ch.seed = strtoull(f[2].c_str(), nullptr, 10);
+            }
+        } else if (f[0] == "jpeg" && f.size() == 2) {
+            if (!parse_number(f[1], v) || v < 1.0 || v > 100.0 || v != floor(v)) return false;
+            ch.kind = 2; ch.param = (float)v;
+        } else return false;
+        out.push_back(ch);
+        names.push_back(item);
+    }
+    return !out.empty();
+}
+
 bool parse_args(int argc, char** argv, Args& A) {
     if (argc < 2) return false;
     A.mode = argv[1];
@@ -111,6 +155,7 @@ bool parse_args(int argc, char** argv, Args& A) {
             case OptKind::Count: A.P.*(o->count) = (uint32_t)std::stoul(value); break;
         }
     }
+    if (!A.robust.empty() && !parse_channels(A.robust, A.channels, A.channel_names)) return false;
     // what each mode cannot do without
     const bool has_secret_source = !A.pass.empty() || !A.keyBase64.empty();
     if (A.mode == "gen-key") return true;
@@ -218,6 +263,41 @@ void report_line(const Args& A, Spectrum& S, const std::vector<uint8_t>& cover, 
     fprintf(stderr, "%s\n", line.c_str());
 }
 
+// the header and payload bytes of a framed stream, out of its repetition code: every 3rd / 7th bit
+void unframe(const std::vector<uint8_t>& bits, std::vector<uint8_t>& header, std::vector<uint8_t>& payload) {
+    std::vector<uint8_t> hb(HEADER_LEN * 8), pb((bits.size() - HEADER_LEN * 24) / 7);
+    for (size_t i = 0; i < hb.size(); i++) hb[i] = bits[3 * i];
+    for (size_t i = 0; i < pb.size(); i++) pb[i] = bits[HEADER_LEN * 24 + 7 * i];
+    header = bytes_from_bits(hb);
+    payload = bytes_from_bits(pb);
+}
+
+// --robust SPEC: one line on stderr -- the bytes just written through every channel of the spec, read back along the walk just used
+// (tfft_robustness_batch; jitter and adaptive alpha through the phase options): raw bit errors of the stream, header and payload byte errors
+// after the repetition code, and whether the message came back.  Never changes the exit code: a refusal is reported on the same line
+void robust_line(const Args& A, Spectrum& S, const std::vector<uint8_t>& stego, const std::vector<tfft_bin>& bins, const std::vector<float>& jit,
+                 const std::vector<uint8_t>& bits) {
+    std::vector<uint8_t> header, payload;
+    unframe(bits, header, payload);
+    const size_t n = A.channels.size();
+    std::vector<uint32_t> res(n * 4);
+    int rc = tfft_set_phase_options(S.ctx, jit.empty() ? nullptr : jit.data(), bins.size(), A.P.adaptive_alpha);
+    if (rc == TFFT_OK)
+        rc = tfft_robustness_batch(S.ctx, 1, stego.data(), S.W, S.H, A.P.center, bins.data(), bins.size(), A.P.alpha, header.data(), payload.data(),
+                                   payload.size(), A.channels.data(), (int)n, 0, res.data());
+    if (rc != TFFT_OK) { fprintf(stderr, "Robustness: not measured (%s)\n", tfft_strerror(rc)); return; }
+    std::string line = "Robustness:";
+    char buf[160];
+    for (size_t k = 0; k < n; k++) {
+        const uint32_t* r = &res[4 * k];
+        const bool ok = r[1] == 0 && r[2] == 0 && (int32_t)r[3] == (int32_t)payload.size() - 16;
+        snprintf(buf, sizeof buf, "%s %s raw=%u/%zu hdr=%u/%u pay=%u/%zu %s", k ? ";" : "", A.channel_names[k].c_str(), r[0], bits.size(), r[1],
+                 (unsigned)HEADER_LEN, r[2], payload.size(), ok ? "ok" : "lost");
+        line += buf;
+    }
+    fprintf(stderr, "%s\n", line.c_str());
+}
+
 void do_embed(const Args& A) {      // S:907-1109
     const bool using_raw_key = !A.keyBase64.empty();
     std::array<uint8_t, 32> master_key{};
@@ -253,12 +333,9 @@ void do_embed(const Args& A) {      // S:907-1109
     }
     std::vector<uint8_t> out((size_t)S.W * S.H * 3);
     if (A.P.fit_crop) {
-        // the walk and jitter above through the fitted batch embed (one image): the stream's header and payload bytes out of its
-        // repetition code, every 3rd / 7th bit
-        std::vector<uint8_t> hb(HEADER_LEN * 8), pb((bits.size() - HEADER_LEN * 24) / 7);
-        for (size_t i = 0; i < hb.size(); i++) hb[i] = bits[3 * i];
-        for (size_t i = 0; i < pb.size(); i++) pb[i] = bits[HEADER_LEN * 24 + 7 * i];
-        const std::vector<uint8_t> header = bytes_from_bits(hb), payload = bytes_from_bits(pb);
+        // the walk and jitter above through the fitted batch embed (one image), with the stream's header and payload bytes
+        std::vector<uint8_t> header, payload;
+        unframe(bits, header, payload);
         int32_t iters = 0;
         uint32_t wrong = 0;
         tf(tfft_embed_stream_batch_fit(S.ctx, 1, rgb.data(), S.W, S.H, A.P.center, bins.data(), jit.empty() ? nullptr : jit.data(), bins.size(),
@@ -274,6 +351,7 @@ void do_embed(const Args& A) {      // S:907-1109
     fprintf(stdout, "Embedded %zu bits into %s (payload %u bytes, ver=2, salt/nonce in header)\n", bits.size(),
             A.outPath.c_str(), (unsigned)A.secret.size());
     if (A.P.report) report_line(A, S, rgb, out);
+    if (!A.channels.empty()) robust_line(A, S, out, bins, jit, bits);
 }
 
 void do_extract(const Args& A) {    // S:1112-1312

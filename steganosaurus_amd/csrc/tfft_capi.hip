@@ -155,6 +155,8 @@ struct tfft_ctx {
     unsigned* bx_idx = nullptr; ExactGroup* bx_grp = nullptr; double2* bx_part = nullptr; ExactVal* bx_val = nullptr; size_t bx_part_cap = 0, bx_val_cap = 0;
     // stego analysis (tfft_phase_hist_batch*, tfft_quality_batch*): per-block partials of a chunk (+ the host forms' results), grown on demand
     void* an_buf = nullptr; size_t an_cap = 0;
+    // robustness analysis (tfft_robustness_batch*): a chunk's attacked images, its decode outputs and the host form's results, grown on demand
+    void* rb_buf = nullptr; size_t rb_cap = 0;
 
     uint8_t* img(int i) const { return img_pool + (size_t)i * img_stride_b; }
     float2* spec(int i) const { return spec_pool + (size_t)i * slot_stride; }
@@ -697,7 +699,7 @@ int tfft_destroy(tfft_ctx* c) {
     (void)hipFree(c->sel); (void)hipFree(c->med); (void)hipFree(c->partial); (void)hipFree(c->amb); (void)hipFree(c->usable); (void)hipFree(c->err); (void)hipFree(c->ex_cand); (void)hipFree(c->ex_val); (void)hipFree(c->ex_below); (void)hipFree(c->ex_n); for (auto& kv : c->ex_table) (void)hipFree(kv.second); (void)hipFree(c->trash); (void)hipFree(c->bit_index); (void)hipFree(c->last_row); (void)hipFree(c->ph_jit);
     (void)hipFree(c->fit_d); (void)hipFree(c->fit_mu); (void)hipFree(c->fit_part); (void)hipFree(c->fit_cnt); (void)hipFree(c->fit_iters); (void)hipFree(c->fit_wrong);
     (void)hipFree(c->bx_win); (void)hipFree(c->bx_cand); (void)hipFree(c->bx_below); (void)hipFree(c->bx_n); (void)hipFree(c->bx_idx); (void)hipFree(c->bx_grp);
-    (void)hipFree(c->bx_part); (void)hipFree(c->bx_val); (void)hipFree(c->an_buf);
+    (void)hipFree(c->bx_part); (void)hipFree(c->bx_val); (void)hipFree(c->an_buf); (void)hipFree(c->rb_buf);
     for (auto& b : c->tb) { (void)hipFree(b.cnt); (void)hipFree(b.off); (void)hipFree(b.ent); (void)hipFree(b.fl); (void)hipFree(b.pb); (void)hipFree(b.jp); }
     for (auto& kv : c->tw) (void)hipFree(kv.second);
     for (auto& kv : c->dc) (void)hipFree(kv.second);
@@ -2641,6 +2643,178 @@ int tfft_quality_batch(tfft_ctx* c, int n_images, const uint8_t* a, const uint8_
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return TFFT_OK;
+}
+
+// ---- robustness analysis: channels over a stego batch, and the errors of what the extractor then reads
+}  // extern "C"
+namespace {
+int channel_ok(const tfft_channel& ch) {
+    switch (ch.kind) {
+        case 0: return TFFT_OK;
+        case 1: return (ch.param >= 0.0f && ch.param < INFINITY) ? TFFT_OK : TFFT_E_INVALID;      // (NaN fails the first compare)
+        case 2: return (ch.param >= 1.0f && ch.param <= 100.0f && ch.param == floorf(ch.param)) ? TFFT_OK : TFFT_E_INVALID;
+        default: return TFFT_E_INVALID;
+    }
+}
+int channel_args(const tfft_ctx* c, int n_images, const void* rgb, int w, int h, const tfft_channel* ch, int n_channels, const void* out) {
+    if (!c || n_images < 1 || !rgb || !out || !ch || n_channels < 1 || w < 1 || h < 1) return TFFT_E_INVALID;
+    for (int k = 0; k < n_channels; k++) if (channel_ok(ch[k])) return TFFT_E_INVALID;
+    if (w > c->max_w || h > c->max_h) return TFFT_E_TOO_LARGE;
+    return TFFT_OK;
+}
+// g packed images (device) through one channel; image 0 of them is image `index0` of the caller's numbering
+int channel_chunk(tfft_ctx* c, const tfft_channel& ch, const uint8_t* in, uint8_t* out, int g, int w, int h, uint64_t index0, hipStream_t st) {
+    const size_t img_bytes = image_bytes(w, h);
+    switch (ch.kind) {
+        case 0:
+            if (in != out) HIPCHK(c, hipMemcpyAsync(out, in, (size_t)g * img_bytes, hipMemcpyDeviceToDevice, st));
+            return TFFT_OK;
+        case 1:
+            HIPCHK(c, launch_channel_awgn(in, out, (size_t)g * img_bytes, ch.seed, index0 * (uint64_t)img_bytes, ch.param, st));
+            return TFFT_OK;
+        default:
+            HIPCHK(c, launch_channel_jpeg(in, out, w, h, g, (int)ch.param, st));
+            return TFFT_OK;
+    }
+}
+
+// the robustness scratch: [results of a chunk, n_channels x n_slots x 4 words (host form)] [status] [header] [payload] [attacked images]
+struct RobustBufs { uint32_t* res; int* status; uint8_t* hdr; uint8_t* pay; uint8_t* img; };
+int ensure_robust(tfft_ctx* c, int n_channels, uint64_t plen, size_t img_bytes, RobustBufs* b) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t n = (size_t)c->n_slots;
+    const size_t o_status = up((size_t)n_channels * n * 16), o_hdr = o_status + up(n * sizeof(int)), o_pay = o_hdr + up(n * kHeaderBytes);
+    const size_t o_img = o_pay + up(n * plen), bytes = o_img + n * img_bytes;
+    if (!c->rb_buf || bytes > c->rb_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));      // an earlier call may still read it (like ensure_analysis: never part of a cached sequence)
+        (void)hipFree(c->rb_buf); c->rb_buf = nullptr; c->rb_cap = 0;
+        const size_t cap = grown(bytes, 4096);
+        int rc = dev_alloc(c, &c->rb_buf, cap);
+        if (rc) return rc;
+        c->rb_cap = cap;
+    }
+    char* p = (char*)c->rb_buf;
+    *b = RobustBufs{(uint32_t*)p, (int*)(p + o_status), (uint8_t*)(p + o_hdr), (uint8_t*)(p + o_pay), (uint8_t*)(p + o_img)};
+    return TFFT_OK;
+}
+int robust_args(const tfft_ctx* c, int n_images, const void* stego, int w, int h, const void* bins, uint64_t n_bins, double alpha, const void* header,
+                const void* payload, uint64_t plen, const tfft_channel* ch, int n_channels, const void* result) {
+    int rc = channel_args(c, n_images, stego, w, h, ch, n_channels, result);
+    if (rc) return rc;
+    if (!bins || !header || (plen && !payload) || !stream_fits(n_bins, plen)) return TFFT_E_INVALID;
+    if (c->ph_adaptive && !(fabs(alpha) < M_PI / 2)) return TFFT_E_INVALID;      // (see extract_chunk)
+    return TFFT_OK;
+}
+// One chunk through every channel: attack (a copy; `none` reads the stego itself), extract every position of the list, decode for the status,
+// count.  stego / hdr / pay: the chunk's own (device); channel k's counts go to res + (k*res_stride)*4, image k.i1 is image index0 of the caller's
+int robust_chunk(tfft_ctx* c, const Chunk& k, const ChunkArgs& a, const uint8_t* stego, const uint8_t* hdr, const uint8_t* pay, uint64_t plen,
+                 int w, int h, const tfft_channel* ch, int n_channels, uint64_t index0, const RobustBufs& b, uint32_t* res, size_t res_stride) {
+    uint8_t* raw = c->stream_bits;      // (no slot offset: the chunks are not split, see for_chunks)
+    for (int q = 0; q < n_channels; q++) {
+        const uint8_t* att = stego;
+        if (ch[q].kind != 0) {
+            int rc = channel_chunk(c, ch[q], stego, b.img, k.g, w, h, index0, k.st);
+            if (rc) return rc;
+            att = b.img;
+        }
+        int rc = extract_chunk(c, k.s0, k.g, k.st, a, att, raw);
+        if (rc) return rc;
+        HIPCHK(c, launch_stream_decode(raw, a.n_bits, plen, k.g, b.hdr, b.pay, b.status, c->stream_plen, k.st));
+        uint32_t* out = res + (size_t)q * res_stride * 4;
+        HIPCHK(c, hipMemsetAsync(out, 0, (size_t)k.g * 4 * sizeof(uint32_t), k.st));
+        HIPCHK(c, launch_robust_count(raw, a.n_bits, hdr, pay, plen, b.status, k.g, out, k.st));
+    }
+    return TFFT_OK;
+}
+}  // namespace
+extern "C" {
+
+int tfft_channel_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, const tfft_channel* ch, uint64_t first_image,
+                           void* rgb_out_dev) {
+    int rc = channel_args(c, n_images, rgb_dev, w, h, ch, 1, rgb_out_dev);
+    if (rc) return rc;
+    const size_t img_bytes = image_bytes(w, h);
+    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
+        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+        rc = channel_chunk(c, *ch, (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, (uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes, g, w, h,
+                           first_image + (uint64_t)i0, c->stream);
+        if (rc) return rc;
+    }
+    return TFFT_OK;
+}
+
+// host buffers: a chunk of n_slots images at a time, attacked in place in the analysis scratch (the slots' image buffers stay as they are)
+int tfft_channel_batch(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int h, const tfft_channel* ch, uint64_t first_image, uint8_t* rgb_out) {
+    int rc = channel_args(c, n_images, rgb, w, h, ch, 1, rgb_out);
+    if (rc) return rc;
+    const size_t img_bytes = image_bytes(w, h);
+    rc = ensure_analysis(c, (size_t)(n_images < c->n_slots ? n_images : c->n_slots) * img_bytes);
+    if (rc) return rc;
+    uint8_t* stage = (uint8_t*)c->an_buf;
+    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
+        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+        HIPCHK(c, hipMemcpyAsync(stage, rgb + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, c->stream));
+        rc = channel_chunk(c, *ch, stage, stage, g, w, h, first_image + (uint64_t)i0, c->stream);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(rgb_out + (size_t)i0 * img_bytes, stage, (size_t)g * img_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return TFFT_OK;
+}
+
+int tfft_robustness_batch_dev(tfft_ctx* c, int n_images, const void* stego_dev, int w, int h, int center, const void* bins_dev, uint64_t n_bins,
+                              double alpha, const void* header_dev, const void* payload_dev, uint64_t payload_len, const tfft_channel* channels,
+                              int n_channels, uint64_t first_image, void* result_out_dev) {
+    int rc = robust_args(c, n_images, stego_dev, w, h, bins_dev, n_bins, alpha, header_dev, payload_dev, payload_len, channels, n_channels, result_out_dev);
+    if (rc) return rc;
+    if (!index_ok(c, n_bins) || !phase_ok(c, n_bins)) return TFFT_E_STATE;
+    const size_t img_bytes = image_bytes(w, h);
+    RobustBufs b;
+    rc = ensure_stream(c, n_bins);
+    if (!rc) rc = ensure_robust(c, 0, payload_len, img_bytes, &b);
+    if (rc) return rc;
+    const ChunkArgs a = ChunkArgs::list(bins_dev, n_bins, alpha);
+    return for_chunks(c, n_images, w, h, center, false, nullptr, [&](const Chunk& k) {
+        return robust_chunk(c, k, a, nth((const uint8_t*)stego_dev, k.i1, img_bytes), nth((const uint8_t*)header_dev, k.i1, kHeaderBytes),
+                            nth((const uint8_t*)payload_dev, k.i1, payload_len), payload_len, w, h, channels, n_channels, first_image + (uint64_t)k.i1, b,
+                            (uint32_t*)result_out_dev + (size_t)k.i1 * 4, (size_t)n_images);
+    });
+}
+
+// host buffers: a chunk of n_slots stegos at a time in the slots' image buffers, the list, the frames and the chunk's counts in the staging
+// buffers of the host pipelines and the robustness scratch
+int tfft_robustness_batch(tfft_ctx* c, int n_images, const uint8_t* stego, int w, int h, int center, const tfft_bin* bins, uint64_t n_bins, double alpha,
+                          const uint8_t* header, const uint8_t* payload, uint64_t payload_len, const tfft_channel* channels, int n_channels,
+                          uint64_t first_image, uint32_t* result_out) {
+    int rc = robust_args(c, n_images, stego, w, h, bins, n_bins, alpha, header, payload, payload_len, channels, n_channels, result_out);
+    if (rc) return rc;
+    if (!index_ok(c, n_bins) || !phase_ok(c, n_bins)) return TFFT_E_STATE;
+    const size_t img_bytes = image_bytes(w, h);
+    RobustBufs b;
+    rc = ensure_stream(c, n_bins);
+    if (!rc) rc = ensure_stream_io(c, payload_len);
+    if (!rc) rc = ensure_stage(c, n_bins);
+    if (!rc) rc = ensure_robust(c, n_channels, payload_len, img_bytes, &b);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->stage_bins, bins, n_bins * sizeof(tfft_bin), hipMemcpyHostToDevice, c->stream));
+    const ChunkArgs a = ChunkArgs::list(c->stage_bins, n_bins, alpha);
+    rc = for_chunks(c, n_images, w, h, center, false, nullptr, [&](const Chunk& k) -> int {
+        hipStream_t st = k.st;
+        for (int i = 0; i < k.g; i++) { c->slots[i].has_spec = false; c->slots[i].rgb_src = nullptr; }      // their images go now
+        HIPCHK(c, hipMemcpyAsync(c->img(0), stego + (size_t)k.i1 * img_bytes, (size_t)k.g * img_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->sio_hdr, header + (size_t)k.i1 * kHeaderBytes, (size_t)k.g * kHeaderBytes, hipMemcpyHostToDevice, st));
+        if (payload_len) HIPCHK(c, hipMemcpyAsync(c->sio_pay, payload + (size_t)k.i1 * payload_len, (size_t)k.g * payload_len, hipMemcpyHostToDevice, st));
+        const int rc1 = robust_chunk(c, k, a, c->img(0), c->sio_hdr, c->sio_pay, payload_len, w, h, channels, n_channels, first_image + (uint64_t)k.i1, b,
+                                     b.res, (size_t)c->n_slots);
+        if (rc1) return rc1;
+        for (int q = 0; q < n_channels; q++)
+            HIPCHK(c, hipMemcpyAsync(result_out + ((size_t)q * n_images + k.i1) * 4, b.res + (size_t)q * c->n_slots * 4, (size_t)k.g * 4 * sizeof(uint32_t),
+                                     hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        return TFFT_OK;
+    });
+    if (rc) return rc;
+    return check_err_flag(c);
 }
 
 void* tfft_host_alloc(size_t bytes) {

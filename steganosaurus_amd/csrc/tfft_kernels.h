@@ -318,4 +318,20 @@ size_t quality_partials(int W, int H);
 hipError_t launch_quality(const uint8_t* a, const uint8_t* b, const QualityParams& P, int n_images, unsigned long long* sse_part, double* ssim_part,
                           unsigned long long* sse_out, double* ssim_out, hipStream_t s);
 
+// ---- robustness analysis: the channels a stego batch goes through, and the error counts of what is read back
+// AWGN over a packed byte stream (in may equal out): byte j of the launch carries counter index0 + j of the noise sequence of `seed`
+hipError_t launch_channel_awgn(const uint8_t* in, uint8_t* out, size_t n_bytes, uint64_t seed, uint64_t index0, float sigma, hipStream_t s);
+// JPEG quantisation of n_images packed W x H RGB8 images (in may equal out): 8 x 8 blocks from (0, 0), 4:4:4, IJG-scaled Annex K tables
+#define TFFT_JQ_COLS 256                 // pixel columns of one workgroup's strip of 8 image rows: 32 blocks, a thread per block row
+#define TFFT_JQ_IN_PITCH 196             // dwords per staged input row: 3 + 768 + 3 bytes, and the 7-dword window of the last thread
+#define TFFT_JQ_OUT_PITCH 194            // dwords per output row: one in front of the 192 of the strip and one behind (the store's byte shift)
+#define TFFT_JQ_TR (32 * 3 * 8 * 9)      // floats of the transpose buffer: 32 blocks x 3 components x 8 rows of pitch 9
+#define TFFT_JQ_LDS ((8 * TFFT_JQ_IN_PITCH + 8 * TFFT_JQ_OUT_PITCH + TFFT_JQ_TR + 128) * 4)
+hipError_t launch_channel_jpeg(const uint8_t* in, uint8_t* out, int W, int H, int n_images, int quality, hipStream_t s);
+// per image: raw bits (n_bins apart) against the Rep-3 / Rep-7 stream of its header (38 bytes) and payload (plen bytes), and the
+// majority decode at that length against the bytes themselves: result[4*img + 0..2] = raw bit errors, header byte errors, payload byte
+// errors (ADDED to what is there: the caller zeroes), result[4*img + 3] = status[img]
+hipError_t launch_robust_count(const uint8_t* raw, uint64_t n_bins, const uint8_t* header, const uint8_t* payload, uint64_t plen,
+                               const int* status, int n_images, uint32_t* result, hipStream_t s);
+
 }  // namespace tfft

@@ -2769,6 +2769,286 @@ hipError_t launch_quality(const uint8_t* a, const uint8_t* b, const QualityParam
     return hipGetLastError();
 }
 
+// ===========================================================================
+// robustness analysis: channels and error counts
+// ===========================================================================
+// splitmix64 (Steele, Lea, Flood 2014; the public-domain reference of S. Vigna, prng.di.unimi.it/splitmix64.c)
+#define TFFT_GOLDEN64 0x9E3779B97F4A7C15ull
+__device__ __forceinline__ uint64_t splitmix64(uint64_t k) {
+    uint64_t z = k + TFFT_GOLDEN64;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// One noisy byte: Box-Muller on the two 24-bit uniforms of the counter's hash, u = (a + 0.5) / 2^24.  Both are formed exactly in fp32: a + 0.5
+// has 25 bits from a = 2^23 on, so the upper half of u1 goes through its complement (-log1p(-(1 - u1)), 1 - u1 exact) -- that is where
+// sqrt(-2 ln u1) is small and a rounded u1 would show (2.4e-4 at u1 = 1 - 2^-25) -- and u2 only sets an angle (its rounding: 4e-7 rad)
+__device__ __forceinline__ unsigned awgn_byte(unsigned pix, uint64_t k, float sigma) {
+    const uint64_t z = splitmix64(k);
+    const unsigned a = (unsigned)(z >> 40), b = (unsigned)(z >> 16) & 0xFFFFFFu;
+    const float e = a < (1u << 23) ? -logf(((float)a + 0.5f) * (1.0f / 16777216.0f))
+                                   : -log1pf(-(((float)(16777216u - a) - 0.5f) * (1.0f / 16777216.0f)));
+    const float g = sqrtf(2.0f * e) * cosf(6.283185307179586f * (((float)b + 0.5f) * (1.0f / 16777216.0f)));
+    const float v = rintf((float)pix + sigma * g);
+    return (unsigned)fminf(fmaxf(v, 0.0f), 255.0f);
+}
+//   grid (ceil((n_bytes/4 + 1)/256))  block 256: a thread owns four bytes -- one aligned dword where input and output share their
+//   alignment (the bytes before the first and after the last aligned dword go to the first threads), four single bytes otherwise
+__global__ void __launch_bounds__(256) k_channel_awgn(const uint8_t* in, uint8_t* out, size_t n_bytes, uint64_t k0, float sigma) {
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    auto one = [&](size_t j) { out[j] = (uint8_t)awgn_byte(in[j], k0 + TFFT_GOLDEN64 * (uint64_t)j, sigma); };
+    if ((((uintptr_t)in ^ (uintptr_t)out) & 3) != 0) {
+        for (size_t j = 4 * gid; j < n_bytes && j < 4 * gid + 4; j++) one(j);
+        return;
+    }
+    size_t head = (size_t)((4 - ((uintptr_t)in & 3)) & 3);
+    if (head > n_bytes) head = n_bytes;
+    const size_t nw = (n_bytes - head) / 4, tail = n_bytes - head - 4 * nw;
+    if (gid < head) one(gid);
+    if (gid < tail) one(head + 4 * nw + gid);
+    if (gid >= nw) return;
+    const size_t j = head + 4 * gid;
+    const uint32_t v = *reinterpret_cast<const uint32_t*>(in + j);
+    uint32_t r = 0;
+#pragma unroll
+    for (int t = 0; t < 4; t++) r |= awgn_byte((v >> (8 * t)) & 0xFFu, k0 + TFFT_GOLDEN64 * (uint64_t)(j + t), sigma) << (8 * t);
+    *reinterpret_cast<uint32_t*>(out + j) = r;
+}
+
+// ITU-T T.81 Annex K, tables K.1 (luminance) and K.2 (chrominance), natural (row-major) order
+__device__ const uint8_t k_jpeg_base[128] = {
+    16, 11, 10, 16, 24, 40, 51, 61,      12, 12, 14, 19, 26, 58, 60, 55,      14, 13, 16, 24, 40, 57, 69, 56,      14, 17, 22, 29, 51, 87, 80, 62,
+    18, 22, 37, 56, 68, 109, 103, 77,    24, 35, 55, 64, 81, 104, 113, 92,    49, 64, 78, 87, 103, 121, 120, 101,  72, 92, 95, 98, 112, 100, 103, 99,
+    17, 18, 24, 47, 99, 99, 99, 99,      18, 21, 26, 66, 99, 99, 99, 99,      24, 26, 56, 99, 99, 99, 99, 99,      47, 66, 99, 99, 99, 99, 99, 99,
+    99, 99, 99, 99, 99, 99, 99, 99,      99, 99, 99, 99, 99, 99, 99, 99,      99, 99, 99, 99, 99, 99, 99, 99,      99, 99, 99, 99, 99, 99, 99, 99};
+
+// orthonormal 8-point DCT-II and its inverse, in place, by the even / odd split: s = x[n] + x[7-n] feeds the even outputs, d = x[n] - x[7-n]
+// the odd ones (22 multiplies each way).  cK = cos(K pi/16) / 2; X[0] carries sqrt(1/8) = c4 / 2 * ... = JC4 per sample
+#define TFFT_JC1 0.49039264020161522f
+#define TFFT_JC2 0.46193976625564337f
+#define TFFT_JC3 0.41573480615127262f
+#define TFFT_JC4 0.35355339059327376f
+#define TFFT_JC5 0.27778511650980111f
+#define TFFT_JC6 0.19134171618254489f
+#define TFFT_JC7 0.09754516100806413f
+__device__ __forceinline__ void dct8(float (&x)[8]) {
+    const float s0 = x[0] + x[7], s1 = x[1] + x[6], s2 = x[2] + x[5], s3 = x[3] + x[4];
+    const float d0 = x[0] - x[7], d1 = x[1] - x[6], d2 = x[2] - x[5], d3 = x[3] - x[4];
+    const float p = s0 + s3, q = s1 + s2, m = s0 - s3, n = s1 - s2;
+    x[0] = TFFT_JC4 * (p + q);
+    x[4] = TFFT_JC4 * (p - q);
+    x[2] = TFFT_JC2 * m + TFFT_JC6 * n;
+    x[6] = TFFT_JC6 * m - TFFT_JC2 * n;
+    x[1] = TFFT_JC1 * d0 + TFFT_JC3 * d1 + TFFT_JC5 * d2 + TFFT_JC7 * d3;
+    x[3] = TFFT_JC3 * d0 - TFFT_JC7 * d1 - TFFT_JC1 * d2 - TFFT_JC5 * d3;
+    x[5] = TFFT_JC5 * d0 - TFFT_JC1 * d1 + TFFT_JC7 * d2 + TFFT_JC3 * d3;
+    x[7] = TFFT_JC7 * d0 - TFFT_JC5 * d1 + TFFT_JC3 * d2 - TFFT_JC1 * d3;
+}
+__device__ __forceinline__ void idct8(float (&x)[8]) {
+    const float a = TFFT_JC4 * (x[0] + x[4]), b = TFFT_JC4 * (x[0] - x[4]);
+    const float c = TFFT_JC2 * x[2] + TFFT_JC6 * x[6], d = TFFT_JC6 * x[2] - TFFT_JC2 * x[6];
+    const float e0 = a + c, e1 = b + d, e2 = b - d, e3 = a - c;
+    const float o0 = TFFT_JC1 * x[1] + TFFT_JC3 * x[3] + TFFT_JC5 * x[5] + TFFT_JC7 * x[7];
+    const float o1 = TFFT_JC3 * x[1] - TFFT_JC7 * x[3] - TFFT_JC1 * x[5] - TFFT_JC5 * x[7];
+    const float o2 = TFFT_JC5 * x[1] - TFFT_JC1 * x[3] + TFFT_JC7 * x[5] + TFFT_JC3 * x[7];
+    const float o3 = TFFT_JC7 * x[1] - TFFT_JC5 * x[3] + TFFT_JC3 * x[5] - TFFT_JC1 * x[7];
+    x[0] = e0 + o0; x[7] = e0 - o0;
+    x[1] = e1 + o1; x[6] = e1 - o1;
+    x[2] = e2 + o2; x[5] = e2 - o2;
+    x[3] = e3 + o3; x[4] = e3 - o3;
+}
+
+// JPEG quantisation.  A workgroup owns a strip of 8 image rows x TFFT_JQ_COLS pixel columns = 32 blocks; thread (block b = tid / 8, line
+// r = tid % 8) holds line r of block b for all three components in registers: first a pixel row (colour transform, row DCT), after a
+// transpose through LDS a coefficient column (column DCT, quantise, dequantise, inverse column DCT), after the transpose back the pixel row
+// again (inverse row DCT, colour transform, rounding).
+// The bytes travel as aligned dwords: the strip's rows are staged in LDS dword for dword as they lie in memory (rows are 3*W bytes
+// apart, so every row has its own byte shift; the dwords that straddle the strip's ends are read byte by byte -- nothing outside the
+// strip's own bytes is touched, which is also what makes in == out safe), a thread cuts its 24 bytes out of seven of them with
+// v_alignbyte_b32, and the results go back the same way through a second strip.  Rows past H and columns past W are the last row /
+// column again (loaded twice; replicated in LDS) and are not stored.
+//   grid (ceil(W/TFFT_JQ_COLS), ceil(H/8), n_images)  block 256   LDS TFFT_JQ_LDS
+__global__ void __launch_bounds__(256) k_channel_jpeg(const uint8_t* in, uint8_t* out, int W, int H, int quality) {
+    uint32_t* sin = reinterpret_cast<uint32_t*>(tfft_smem);                   // [8][TFFT_JQ_IN_PITCH]
+    uint32_t* sout = sin + 8 * TFFT_JQ_IN_PITCH;                              // [8][TFFT_JQ_OUT_PITCH], the strip's dword d at [1 + d]
+    float* tr = reinterpret_cast<float*>(sout + 8 * TFFT_JQ_OUT_PITCH);       // [32][3][8][9]
+    float* ql = tr + TFFT_JQ_TR;                                              // [2][64]
+    uint8_t* sinb = reinterpret_cast<uint8_t*>(sin);
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * TFFT_JQ_COLS, y0 = blockIdx.y * 8;
+    const int ncols = W - x0 < TFFT_JQ_COLS ? W - x0 : TFFT_JQ_COLS, nb = 3 * ncols;
+    const size_t img_off = (size_t)blockIdx.z * (size_t)W * (size_t)H * 3;
+    // the quantiser of this quality (IJG scaling), as floats
+    if (tid < 128) {
+        const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+        int q = ((int)k_jpeg_base[tid] * s + 50) / 100;
+        q = q < 1 ? 1 : (q > 255 ? 255 : q);
+        ql[tid] = (float)q;
+    }
+    // ---- stage the 8 rows
+    constexpr int ND = (3 + 3 * TFFT_JQ_COLS + 3) / 4;      // dwords a row of the strip can touch
+    for (int e = tid; e < 8 * ND; e += 256) {
+        const int r = e / ND, d = e - r * ND;
+        const int y = y0 + r < H ? y0 + r : H - 1;
+        const uint8_t* row = in + img_off + ((size_t)y * W + x0) * 3;
+        const int sh = (int)((uintptr_t)row & 3), lo = 4 * d - sh;      // the dword holds bytes lo .. lo+3 of the row
+        if (lo >= 0 && lo + 4 <= nb) sin[r * TFFT_JQ_IN_PITCH + d] = *reinterpret_cast<const uint32_t*>(row + lo);
+        else
+            for (int t = 0; t < 4; t++)
+                if (lo + t >= 0 && lo + t < nb) sinb[4 * (r * TFFT_JQ_IN_PITCH + d) + t] = row[lo + t];
+    }
+    __syncthreads();
+    const int full = (ncols + 7) & ~7;
+    if (full != ncols) {      // the last column again, up to the end of its block
+        for (int e = tid; e < 8 * 21; e += 256) {
+            const int r = e / 21, j = e - r * 21, px = ncols + j / 3, ch = j % 3;
+            const int y = y0 + r < H ? y0 + r : H - 1;
+            const int sh = (int)((uintptr_t)(in + img_off + ((size_t)y * W + x0) * 3) & 3);
+            if (px < full) sinb[4 * r * TFFT_JQ_IN_PITCH + sh + 3 * px + ch] = sinb[4 * r * TFFT_JQ_IN_PITCH + sh + 3 * (ncols - 1) + ch];
+        }
+        __syncthreads();
+    }
+    const int b = tid >> 3, r = tid & 7;
+    const bool active = 8 * b < ncols;
+    float* tb = tr + b * (3 * 8 * 9);
+    float Y[8], Cb[8], Cr[8];
+    if (active) {
+        const int y = y0 + r < H ? y0 + r : H - 1;
+        const int sh = (int)((uintptr_t)(in + img_off + ((size_t)y * W + x0) * 3) & 3);
+        const int o = sh + 24 * b;
+        const uint32_t* w = sin + r * TFFT_JQ_IN_PITCH + (o >> 2);
+        uint32_t v[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) v[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], (uint32_t)(o & 3));
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const float R = (float)((v[(3 * j) >> 2] >> (8 * ((3 * j) & 3))) & 0xFFu);
+            const float G = (float)((v[(3 * j + 1) >> 2] >> (8 * ((3 * j + 1) & 3))) & 0xFFu);
+            const float B = (float)((v[(3 * j + 2) >> 2] >> (8 * ((3 * j + 2) & 3))) & 0xFFu);
+            // JFIF full-range BT.601
+            Y[j] = 0.299f * R + 0.587f * G + 0.114f * B - 128.0f;
+            Cb[j] = -0.168736f * R - 0.331264f * G + 0.5f * B;
+            Cr[j] = 0.5f * R - 0.418688f * G - 0.081312f * B;
+        }
+        dct8(Y); dct8(Cb); dct8(Cr);
+#pragma unroll
+        for (int u = 0; u < 8; u++) { tb[(0 * 8 + r) * 9 + u] = Y[u]; tb[(1 * 8 + r) * 9 + u] = Cb[u]; tb[(2 * 8 + r) * 9 + u] = Cr[u]; }
+    }
+    __syncthreads();
+    if (active) {      // column r of the block: coefficients (v, u = r), quantiser ql[8*v + r]
+#pragma unroll
+        for (int k = 0; k < 8; k++) { Y[k] = tb[(0 * 8 + k) * 9 + r]; Cb[k] = tb[(1 * 8 + k) * 9 + r]; Cr[k] = tb[(2 * 8 + k) * 9 + r]; }
+        dct8(Y); dct8(Cb); dct8(Cr);
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const float qy = ql[8 * k + r], qc = ql[64 + 8 * k + r];
+            Y[k] = rintf(Y[k] / qy) * qy; Cb[k] = rintf(Cb[k] / qc) * qc; Cr[k] = rintf(Cr[k] / qc) * qc;
+        }
+        idct8(Y); idct8(Cb); idct8(Cr);
+    }
+    __syncthreads();      // every column has been read: the buffer takes the half-inverted block
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) { tb[(0 * 8 + k) * 9 + r] = Y[k]; tb[(1 * 8 + k) * 9 + r] = Cb[k]; tb[(2 * 8 + k) * 9 + r] = Cr[k]; }
+    }
+    __syncthreads();
+    if (active) {
+#pragma unroll
+        for (int u = 0; u < 8; u++) { Y[u] = tb[(0 * 8 + r) * 9 + u]; Cb[u] = tb[(1 * 8 + r) * 9 + u]; Cr[u] = tb[(2 * 8 + r) * 9 + u]; }
+        idct8(Y); idct8(Cb); idct8(Cr);
+        uint32_t v[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const float yy = Y[j] + 128.0f;
+            const float R = yy + 1.402f * Cr[j];
+            const float G = yy - 0.344136f * Cb[j] - 0.714136f * Cr[j];
+            const float B = yy + 1.772f * Cb[j];
+            v[(3 * j) >> 2] |= (uint32_t)fminf(fmaxf(rintf(R), 0.0f), 255.0f) << (8 * ((3 * j) & 3));
+            v[(3 * j + 1) >> 2] |= (uint32_t)fminf(fmaxf(rintf(G), 0.0f), 255.0f) << (8 * ((3 * j + 1) & 3));
+            v[(3 * j + 2) >> 2] |= (uint32_t)fminf(fmaxf(rintf(B), 0.0f), 255.0f) << (8 * ((3 * j + 2) & 3));
+        }
+#pragma unroll
+        for (int i = 0; i < 6; i++) sout[r * TFFT_JQ_OUT_PITCH + 1 + 6 * b + i] = v[i];
+    }
+    __syncthreads();
+    // ---- store the rows < H: aligned dword d of a row holds the strip's bytes 4d - sh .. 4d - sh + 3
+    for (int e = tid; e < 8 * ND; e += 256) {
+        const int rr = e / ND, d = e - rr * ND;
+        if (y0 + rr >= H) break;
+        uint8_t* row = out + img_off + ((size_t)(y0 + rr) * W + x0) * 3;
+        const int sh = (int)((uintptr_t)row & 3), lo = 4 * d - sh;
+        if (lo >= nb) continue;
+        const uint32_t hi = sout[rr * TFFT_JQ_OUT_PITCH + 1 + d], low = sout[rr * TFFT_JQ_OUT_PITCH + d];
+        const uint32_t val = sh ? __builtin_amdgcn_alignbyte(hi, low, (uint32_t)(4 - sh)) : hi;
+        if (lo >= 0 && lo + 4 <= nb) *reinterpret_cast<uint32_t*>(row + lo) = val;
+        else
+            for (int t = 0; t < 4; t++)
+                if (lo + t >= 0 && lo + t < nb) row[lo + t] = (uint8_t)(val >> (8 * t));
+    }
+}
+
+// The error counts of one attacked batch.  A thread takes one byte of the frame (38 header bytes, then plen payload bytes): the 24 or
+// 56 raw bits that carry its 8 bits three or seven times over (Rep-3 / Rep-7, MSB first: frame_bit's layout) are compared with those bits,
+// their majorities with the byte.  Counts are integers: block sums in LDS, then one atomic add per counter and block.
+//   grid (ceil((38 + plen)/256) capped at 64, n_images)  block 256
+__global__ void __launch_bounds__(256) k_robust_count(const uint8_t* __restrict__ raw, uint64_t n_bins, const uint8_t* __restrict__ header,
+                                                      const uint8_t* __restrict__ payload, uint64_t plen, const int* __restrict__ status,
+                                                      uint32_t* __restrict__ result) {
+    unsigned* red = reinterpret_cast<unsigned*>(tfft_smem);      // [3][256]
+    const int tid = threadIdx.x;
+    const uint64_t img = blockIdx.y;
+    const uint8_t* in = raw + img * n_bins;
+    unsigned n_raw = 0, n_hdr = 0, n_pay = 0;
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + tid; j < 38 + plen; j += (uint64_t)gridDim.x * 256) {
+        const bool hd = j < 38;
+        const int rep = hd ? 3 : 7;
+        const uint8_t* p = hd ? in + j * 24 : in + 912 + (j - 38) * 56;
+        const unsigned want = hd ? header[img * 38 + j] : payload[img * plen + (j - 38)];
+        unsigned v = 0;
+        for (int q = 0; q < 8; q++, p += rep) {
+            unsigned ones = 0;
+            for (int t = 0; t < rep; t++) ones += p[t] ? 1u : 0u;
+            n_raw += ((want >> (7 - q)) & 1u) ? rep - ones : ones;
+            v = (v << 1) | (2 * ones > (unsigned)rep ? 1u : 0u);
+        }
+        if (v != want) { if (hd) n_hdr++; else n_pay++; }
+    }
+    red[tid] = n_raw; red[256 + tid] = n_hdr; red[512 + tid] = n_pay;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) { red[tid] += red[tid + s]; red[256 + tid] += red[256 + tid + s]; red[512 + tid] += red[512 + tid + s]; }
+        __syncthreads();
+    }
+    if (tid < 3 && red[256 * tid]) atomicAdd(result + 4 * img + tid, red[256 * tid]);
+    if (tid == 3 && blockIdx.x == 0) result[4 * img + 3] = (uint32_t)status[img];
+}
+
+hipError_t launch_channel_awgn(const uint8_t* in, uint8_t* out, size_t n_bytes, uint64_t seed, uint64_t index0, float sigma, hipStream_t s) {
+    if (n_bytes == 0) return hipSuccess;
+    const size_t blocks = (n_bytes / 4 + 1 + 255) / 256;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_channel_awgn, dim3((unsigned)blocks), dim3(256), 0, s, in, out, n_bytes, seed + TFFT_GOLDEN64 * index0, sigma);
+    return hipGetLastError();
+}
+
+hipError_t launch_channel_jpeg(const uint8_t* in, uint8_t* out, int W, int H, int n_images, int quality, hipStream_t s) {
+    if (W < 1 || H < 1 || n_images < 1 || n_images > 65535 || quality < 1 || quality > 100) return hipErrorInvalidValue;
+    const unsigned gx = (unsigned)((W + TFFT_JQ_COLS - 1) / TFFT_JQ_COLS), gy = (unsigned)((H + 7) / 8);
+    if (gy > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_channel_jpeg, dim3(gx, gy, n_images), dim3(256), TFFT_JQ_LDS, s, in, out, W, H, quality);
+    return hipGetLastError();
+}
+
+hipError_t launch_robust_count(const uint8_t* raw, uint64_t n_bins, const uint8_t* header, const uint8_t* payload, uint64_t plen,
+                               const int* status, int n_images, uint32_t* result, hipStream_t s) {
+    if (n_images < 1 || n_images > 65535 || n_bins < 912 + 56 * plen) return hipErrorInvalidValue;
+    uint64_t nb = (38 + plen + 255) / 256;
+    if (nb > 64) nb = 64;
+    hipLaunchKernelGGL(k_robust_count, dim3((unsigned)nb, n_images), dim3(256), 3 * 256 * sizeof(unsigned), s, raw, n_bins, header, payload, plen,
+                       status, result);
+    return hipGetLastError();
+}
+
 }  // namespace tfft
 
 // tfft_stats.hip is a unit of its own: hipcc compiles it apart (csrc/Makefile), and so does the CPU emulation of the tests

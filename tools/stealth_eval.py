@@ -11,8 +11,15 @@
           256-bin annulus phase histograms: KL against the pooled histogram of a disjoint set of reference covers (analysis.kl_divergence)
           and the mass in the +-alpha bins (analysis.peak_mass).  AUC (analysis.auc: stego positive, covers negative) per cell and score,
           PSNR / SSIM medians.
+  --robust  what a one-shot stego survives, on synthetic covers (synth.cover_rgb, NOT photographs): 32 stegos of
+          1920 x 1080 (default alpha 0.5 and density 0.7, a 4 KB payload, one shared walk) through tfft_robustness_batch_dev with AWGN of
+          sigma 0.5, 1, 2, 4, 8 and JPEG quantisation at Q 95, 90, 75, 50: mean raw BER, mean byte error rate after the repetition code,
+          share of images whose message came back.  Cost, measured like --cost (legs alternated in one process, median over rounds): the
+          channel kernels alone, the robustness call with one channel and with all of them, against tfft_extract_stream_batch_dev on the
+          same batch.
 
     python tools/stealth_eval.py --cost [--rounds 5 --steps 5]
+    python tools/stealth_eval.py --robust [--rounds 5 --steps 5]
     python tools/stealth_eval.py --auc [--n 256 --n-ref 64 --payload 4096] [--out FILE.json]
 One JSON line on stdout (and in --out)."""
 import argparse
@@ -172,8 +179,78 @@ def auc_cells(n, n_ref, chunk, seed0, plen=PLEN):
             "n_ref": n_ref, "cells": res}
 
 
+def robust(rounds, steps, warmup, plen=PLEN):
+    import torch
+    from steganosaurus_amd import analysis as A
+    from steganosaurus_amd import binding as B
+    from steganosaurus_amd.synth import cover_rgb
+    w, h, nimg, slots = 1920, 1080, 32, 16
+    n_bins = 912 + 56 * plen
+    bins = B.Walk(bytes(range(32)), next_pow2(h), next_pow2(w)).next(n_bins)
+    sbins, idx = B.bins_sort(bins)
+    dev = "cuda:0"
+    covers = torch.from_numpy(np.stack([cover_rgb(w, h, i) for i in range(nimg)])).to(dev)
+    stego = torch.empty_like(covers)
+    scratch = torch.empty_like(covers)
+    d_bins = torch.from_numpy(sbins.view(np.uint8).reshape(-1, 8).copy()).to(dev)
+    rng = np.random.default_rng(0)
+    d_hdr = torch.from_numpy(np.tile(header(plen), nimg)).to(dev)
+    d_pay = torch.from_numpy(rng.integers(0, 256, nimg * plen).astype(np.uint8)).to(dev)
+    o_hdr = torch.empty(nimg * 38, dtype=torch.uint8, device=dev)
+    o_pay = torch.empty(nimg * plen, dtype=torch.uint8, device=dev)
+    o_st = torch.empty(nimg, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    ctx = B.Context(w, h, slots=slots)
+    ctx.set_bit_index(idx)
+    ctx.bins_register_dev(d_bins.data_ptr(), n_bins)
+    ctx.embed_stream_batch_dev(nimg, covers.data_ptr(), w, h, d_bins.data_ptr(), n_bins, d_hdr.data_ptr(), d_pay.data_ptr(), plen, stego.data_ptr())
+    ctx.sync()
+    rows = [("none",)] + [("awgn", s, 1) for s in (0.5, 1.0, 2.0, 4.0, 8.0)] + [("jpeg", q) for q in (95, 90, 75, 50)]
+    d_res = torch.empty(len(rows) * nimg * 4, dtype=torch.int32, device=dev)
+
+    def rb(chs):
+        ctx.robustness_batch_dev(nimg, stego.data_ptr(), w, h, d_bins.data_ptr(), n_bins, d_hdr.data_ptr(), d_pay.data_ptr(), plen, chs, d_res.data_ptr())
+    rb(rows)
+    ctx.sync()
+    r = d_res.cpu().numpy().view(np.uint32).reshape(len(rows), nimg, 4)
+    table = {}
+    for k, ch in enumerate(rows):
+        name = ":".join(str(v) for v in ch[:2])
+        table[name] = {"raw_ber": round(float(A.raw_ber(r[k], plen).mean()), 6), "byte_error_rate": round(float(A.byte_error_rate(r[k], plen).mean()), 6),
+                       "recovered_share": round(float(A.recovered(r[k], plen).mean()), 4)}
+    legs = {
+        "extract_stream": lambda: ctx.extract_stream_batch_dev(nimg, stego.data_ptr(), w, h, d_bins.data_ptr(), n_bins, o_hdr.data_ptr(),
+                                                               o_pay.data_ptr(), plen, o_st.data_ptr()),
+        "channel_awgn": lambda: ctx.channel_batch_dev(nimg, stego.data_ptr(), w, h, ("awgn", 2.0, 1), scratch.data_ptr()),
+        "channel_jpeg": lambda: ctx.channel_batch_dev(nimg, stego.data_ptr(), w, h, ("jpeg", 75), scratch.data_ptr()),
+        "robust_none": lambda: rb([("none",)]),
+        "robust_awgn": lambda: rb([("awgn", 2.0, 1)]),
+        "robust_jpeg": lambda: rb([("jpeg", 75)]),
+        "robust_all_%d" % len(rows): lambda: rb(rows),
+    }
+    ms = {leg: [] for leg in legs}
+    for _ in range(rounds):
+        for leg, fn in legs.items():
+            for _ in range(warmup):
+                fn()
+            ctx.sync()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                fn()
+            ctx.sync()
+            ms[leg].append((time.perf_counter() - t0) * 1e3 / steps)
+    ctx.close()
+    out = {leg: {"ms_per_call": round(statistics.median(v), 4), "ms_all_rounds": [round(x, 4) for x in v]} for leg, v in ms.items()}
+    base = out["extract_stream"]["ms_per_call"]
+    for leg in legs:
+        out[leg]["vs_extract"] = round(out[leg]["ms_per_call"] / base, 4)
+    return {"image": [w, h], "images_per_call": nimg, "slots": slots, "covers": "synth.cover_rgb (synthetic, not photographs)", "alpha": 0.5,
+            "density": 0.7, "payload_bytes": plen, "table": table, "legs": out}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--robust", action="store_true")
     ap.add_argument("--cost", action="store_true")
     ap.add_argument("--auc", action="store_true")
     ap.add_argument("--rounds", type=int, default=5)
@@ -195,6 +272,8 @@ def main():
         res["cost"] = {wl: cost(wl, a.rounds, a.steps, a.warmup) for wl in a.workloads.split(",")}
     if a.auc:
         res["auc"] = auc_cells(a.n, a.n_ref, a.chunk, a.seed, a.payload + 16)
+    if a.robust:
+        res["robust"] = robust(a.rounds, a.steps, a.warmup)
     line = json.dumps(res)
     print(line, flush=True)
     if a.out:
