@@ -387,6 +387,27 @@ int tfft_robustness_batch(tfft_ctx* ctx, int n_images, const uint8_t* stego, int
                           const uint8_t* header, const uint8_t* payload, uint64_t payload_len,
                           const tfft_channel* channels, int n_channels, uint64_t first_image, uint32_t* result_out);
 
+/* ------------------------------------------------------------ blind steganalysis features
+ * SPAM (Pevny, Bas, Fridrich 2010), second order: co-occurrence counts of clamped differences of neighbouring pixels, the features of a
+ * spatial-domain steganalyser that knows nothing of the embedding.  Pure integer arithmetic on the pixels.
+ * For one plane I of a packed RGB8 image of w x h, a truncation t in 1..4 and n = 2t + 1, four directions d = (dy, dx) are counted, in
+ * this order: 0 right (0, 1), 1 down (1, 0), 2 down-right (1, 1), 3 down-left (1, -1).  For every pixel p = (y, x) with p + 3d inside the
+ * image:
+ *     e_k = clamp(I[p + (k-1)d] - I[p + kd], -t, t)   k = 1, 2, 3
+ *     idx = ((e1 + t) n + (e2 + t)) n + (e3 + t)
+ *     counts[image][plane][dir][idx] += 1
+ * counts_out: uint32 [n_images][3][4][n^3] (686 * 6 words per image at t = 3).  Every entry is written; a direction with no triple (w < 4
+ * or h < 4) is all zeros; direction d sums to max(0, h - 3|dy|) * max(0, w - 3|dx|).  The four opposite directions are not counted: they
+ * are an index permutation, C_{-d}[a, b, c] = C_d[-c, -b, -a] (steganosaurus_amd/analysis.py: spam_features applies it and normalises as
+ * the released extractor does, 2 n^3 features per plane).
+ * Images are packed, image i at + i*w*h*3; only those n_images*w*h*3 bytes are read.  t outside 1..4, n_images < 1, w or h < 1:
+ * TFFT_E_INVALID; w > max_w or h > max_h: TFFT_E_TOO_LARGE.  The calls leave the slots alone (like tfft_quality_batch): spectra, image
+ * buffers, tfft_medians, tfft_capacity and tfft_lowfreq_mag of a resident image are as before.  Results do not depend on n_slots, and
+ * repeated calls return identical bytes.  The _dev form does not synchronise (it needs no scratch); the host form stages one chunk of
+ * n_slots images at a time in the analysis scratch and synchronises. */
+int tfft_spam_batch_dev(tfft_ctx* ctx, int n_images, const void* rgb_dev, int w, int h, int t, void* counts_out_dev);
+int tfft_spam_batch(tfft_ctx* ctx, int n_images, const uint8_t* rgb, int w, int h, int t, uint32_t* counts_out);
+
 /* --------------------------------------------------------- keyed walk (HOST)
  * KS + Turtle + the density gate (S:665-695, S:749-810, S:1076-1081): a
  * resumable generator of embedding positions.  Pure host code, no device.

@@ -8,6 +8,9 @@ The histograms come from ``Context.phase_hist_batch_*`` (tfft_phase_hist_batch[_
   auc           the Mann-Whitney statistic: P(pos > neg) + P(pos == neg) / 2
 and from the counts of ``Context.robustness_batch_*`` (tfft_robustness_batch[_dev]):
   raw_ber, byte_error_rate, recovered   raw bit error rate, byte error rate after the repetition code, and whether the message came back
+and from the counts of ``Context.spam_batch_*`` (tfft_spam_batch[_dev]):
+  spam_features        the 2 n^3 SPAM features per plane: the released extractor's normalisation and direction averaging
+  fld_fit, fld_score   a Fisher linear discriminant with a ridge, the simple classifier the features are judged with
 """
 import numpy as np
 
@@ -69,6 +72,47 @@ def recovered(result, payload_len):
     announces, payload_len - 16"""
     r = np.asarray(result)
     return (r[..., 1] == 0) & (r[..., 2] == 0) & (r[..., 3].astype(np.int64) == int(payload_len) - 16)
+
+
+# ---- blind steganalysis (DESIGN.md section 14): SPAM features from the (..., 3, 4, n^3) uint32 counts of Context.spam_batch_*
+def spam_features(counts, t=3):
+    """(..., 3, 4, n^3) counts of the directions right, down, down-right, down-left -> (..., 3, 2 n^3) float64, n = 2t + 1.
+    M_d = C_d / sum(C_d) for each of the eight directions (0 where the sum is 0); the four that are not counted are an index
+    permutation, C_{-d}[a, b, c] = C_d[-c, -b, -a].  The first n^3 entries are the mean of M over right, left, down, up, the last n^3
+    the mean over the four diagonals."""
+    n = 2 * int(t) + 1
+    c = np.asarray(counts, np.float64)
+    if c.shape[-3:] != (3, 4, n ** 3):
+        raise ValueError("spam_features: counts of shape (..., 3, 4, %d) wanted, got %r" % (n ** 3, c.shape))
+    tot = c.sum(axis=-1, keepdims=True)
+    m = np.where(tot > 0, c / np.where(tot > 0, tot, 1.0), 0.0)
+    cube = m.reshape(m.shape[:-1] + (n, n, n))
+    opp = np.swapaxes(cube[..., ::-1, ::-1, ::-1], -1, -3).reshape(m.shape)      # [a, b, c] <- [-c, -b, -a]
+    both = m + opp
+    return np.concatenate([(both[..., 0, :] + both[..., 1, :]) / 4.0, (both[..., 2, :] + both[..., 3, :]) / 4.0], axis=-1)
+
+
+def fld_fit(pos, neg, ridge=1e-3):
+    """Fisher linear discriminant of two (samples, d) classes -> (w, b): S the pooled within-class covariance (divisor n_pos + n_neg - 2),
+    lambda = ridge * trace(S) / d (1 if the trace is 0), w = solve(S + lambda I, mu_pos - mu_neg), b = -w . (mu_pos + mu_neg) / 2"""
+    pos = np.atleast_2d(np.asarray(pos, np.float64))
+    neg = np.atleast_2d(np.asarray(neg, np.float64))
+    d = pos.shape[1]
+    if neg.shape[1] != d or pos.shape[0] + neg.shape[0] < 3:
+        raise ValueError("fld_fit needs two classes of the same width and at least three samples")
+    mp, mn = pos.mean(axis=0), neg.mean(axis=0)
+    dp, dn = pos - mp, neg - mn
+    s = (dp.T @ dp + dn.T @ dn) / float(pos.shape[0] + neg.shape[0] - 2)
+    tr = float(np.trace(s))
+    lam = ridge * tr / d if tr != 0.0 else 1.0
+    w = np.linalg.solve(s + lam * np.eye(d), mp - mn)
+    return w, float(-w @ (mp + mn) / 2.0)
+
+
+def fld_score(x, model):
+    """x . w + b for the (w, b) of fld_fit: positive on the side of its first class"""
+    w, b = model
+    return np.asarray(x, np.float64) @ w + b
 
 
 def auc(pos_scores, neg_scores):

@@ -93,6 +93,8 @@ SYMBOLS = {
     "tfft_channel_batch": (_i, [_vp, _i, _vp, _i, _i, _vp, _u64, _vp]),
     "tfft_robustness_batch_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _u64, _d, _vp, _vp, _u64, _vp, _i, _u64, _vp]),
     "tfft_robustness_batch": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _u64, _d, _vp, _vp, _u64, _vp, _i, _u64, _vp]),
+    "tfft_spam_batch_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
+    "tfft_spam_batch": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
     "tfft_profile_stage": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _u64, _d, C.POINTER(C.c_float), _pi]),
     "tfft_timer_begin": (_i, [_vp]),
     "tfft_timer_end": (_i, [_vp, C.POINTER(C.c_float)]),
@@ -555,6 +557,20 @@ class Context:
         _check(self.lib.tfft_robustness_batch(self.h, n, _ptr(stego), w, h, int(center), _ptr(bins), len(bins), alpha, _ptr(header),
                                               _ptr(payload), payload.shape[1], _ptr(ch), len(ch), first_image, _ptr(out)),
                "tfft_robustness_batch")
+        return out
+
+    # ---- SPAM steganalysis features ------------------------------------------------------------
+    def spam_batch_dev(self, n_images, rgb_ptr, w, h, counts_ptr, t=3):
+        """counts (device): uint32 [n_images][3][4][(2t+1)^3] difference co-occurrences of n packed images (device)"""
+        _check(self.lib.tfft_spam_batch_dev(self.h, n_images, _ptr(rgb_ptr), w, h, t, _ptr(counts_ptr)), "tfft_spam_batch_dev")
+
+    def spam_batch_host(self, rgb, t=3):
+        """rgb: (n,H,W,3) uint8 host array -> (n, 3, 4, (2t+1)^3) uint32"""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        n, h, w = rgb.shape[:3]
+        # (an invalid t is the library's to refuse: room for the largest valid one)
+        out = np.zeros((n, 3, 4, (2 * t + 1) ** 3 if 1 <= t <= 4 else 1), np.uint32)
+        _check(self.lib.tfft_spam_batch(self.h, n, _ptr(rgb), w, h, t, _ptr(out)), "tfft_spam_batch")
         return out
 
     STAGES = ["rows_fwd", "cols_fwd_a", "cols_fwd_b", "embed", "cols_inv_a", "cols_inv_b", "rows_inv", "read",

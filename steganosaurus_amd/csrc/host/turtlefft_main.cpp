@@ -60,6 +60,9 @@ void usage() {
             "                      SPEC = comma list of none | awgn:SIGMA[:SEED] | jpeg:Q   (e.g. none,awgn:2:7,jpeg:75)\n"
             "  turtlefft extract --in stego.png (--pass PW | --key KEY_BASE64)\n"
             "      [same tuning options as embed]\n"
+            "  turtlefft spam    --in image.png\n"
+            "      Print the 686 second-order SPAM features (T = 3) of each plane, one line R, G, B: what a blind\n"
+            "      spatial-domain steganalyser's classifier eats.\n"
             "  The 2-D FFT / phase embedding runs on an AMD MI355X through libturtlefft_hip.so.\n");
 }
 
@@ -160,6 +163,7 @@ bool parse_args(int argc, char** argv, Args& A) {
     const bool has_secret_source = !A.pass.empty() || !A.keyBase64.empty();
     if (A.mode == "gen-key") return true;
     if (A.mode == "extract") return !A.inPath.empty() && has_secret_source;
+    if (A.mode == "spam") return !A.inPath.empty();
     if (A.mode == "embed") return !A.inPath.empty() && has_secret_source && !A.outPath.empty() && !A.secret.empty();
     return false;
 }
@@ -422,6 +426,44 @@ void do_extract(const Args& A) {    // S:1112-1312
     printf("%s\n", secret.c_str());
 }
 
+// `spam --in IMAGE`, not in the reference: the SPAM features of steganosaurus_amd.analysis.spam_features at T = 3, from
+// the counts of tfft_spam_batch -- per direction M = C / sum(C) (0 for an empty direction), the opposite direction by the index
+// permutation [a, b, c] <- [-c, -b, -a], the mean over right, left, down, up and then over the four diagonals
+void do_spam(const Args& A) {
+    constexpr int T = 3, N = 2 * T + 1, N3 = N * N * N;
+    int W = 0, H = 0;
+    std::vector<uint8_t> rgb;
+    if (!load_rgb8(A.inPath, rgb, W, H)) die("Failed to load %s", A.inPath.c_str());
+    int dev = 0;
+    if (const char* e = getenv("TURTLEFFT_DEVICE")) dev = atoi(e);
+    tfft_ctx* ctx = nullptr;
+    tf(tfft_create(dev, W, H, 1, &ctx), "turtlefft: cannot open the GPU context");
+    std::vector<uint32_t> counts((size_t)3 * 4 * N3);
+    tf(tfft_spam_batch(ctx, 1, rgb.data(), W, H, T, counts.data()), "spam");
+    tfft_destroy(ctx);
+    const char* names[3] = {"R", "G", "B"};
+    for (int p = 0; p < 3; p++) {
+        std::vector<double> both((size_t)4 * N3, 0.0);      // M_d + M_{-d}
+        for (int d = 0; d < 4; d++) {
+            const uint32_t* c = &counts[(size_t)(p * 4 + d) * N3];
+            double tot = 0.0;
+            for (int i = 0; i < N3; i++) tot += (double)c[i];
+            if (tot <= 0.0) continue;
+            for (int a = 0; a < N; a++)
+                for (int b = 0; b < N; b++)
+                    for (int e = 0; e < N; e++) {
+                        const int i = (a * N + b) * N + e, o = ((N - 1 - e) * N + (N - 1 - b)) * N + (N - 1 - a);
+                        both[(size_t)d * N3 + i] = (double)c[i] / tot + (double)c[o] / tot;
+                    }
+        }
+        fputs(names[p], stdout);
+        for (int half = 0; half < 2; half++)
+            for (int i = 0; i < N3; i++)
+                printf(" %.9e", (both[(size_t)(2 * half) * N3 + i] + both[(size_t)(2 * half + 1) * N3 + i]) / 4.0);
+        fputc('\n', stdout);
+    }
+}
+
 void do_gen_key(const Args& A) {    // S:1315-1416
     std::array<uint8_t, 32> master{};
     if (!random_bytes(master.data(), 32)) die("Failed to generate random key (CSPRNG error)");
@@ -467,6 +509,7 @@ int main(int argc, char** argv) {
     }
     if (A.mode == "gen-key") do_gen_key(A);
     else if (A.mode == "embed") do_embed(A);
+    else if (A.mode == "spam") do_spam(A);
     else do_extract(A);
     return 0;
 }

@@ -2817,6 +2817,52 @@ int tfft_robustness_batch(tfft_ctx* c, int n_images, const uint8_t* stego, int w
     return check_err_flag(c);
 }
 
+// ---- SPAM steganalysis features: co-occurrence counts of clamped pixel differences, straight from the image bytes
+}  // extern "C"
+namespace {
+int spam_args(const tfft_ctx* c, int n_images, const void* rgb, int w, int h, int t, const void* out) {
+    if (!c || n_images < 1 || !rgb || !out || w < 1 || h < 1 || t < 1 || t > 4) return TFFT_E_INVALID;
+    if (w > c->max_w || h > c->max_h) return TFFT_E_TOO_LARGE;
+    return TFFT_OK;
+}
+size_t spam_words(int t) { const size_t n = 2 * (size_t)t + 1; return 12 * n * n * n; }
+}  // namespace
+extern "C" {
+
+// no scratch and no slot: the images are read where they lie (a launch takes at most 65535 of them)
+int tfft_spam_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int t, void* counts_out_dev) {
+    int rc = spam_args(c, n_images, rgb_dev, w, h, t, counts_out_dev);
+    if (rc) return rc;
+    const size_t img_bytes = image_bytes(w, h), words = spam_words(t);
+    for (int i0 = 0; i0 < n_images; i0 += 65535) {
+        const int g = n_images - i0 < 65535 ? n_images - i0 : 65535;
+        HIPCHK(c, launch_spam((const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, w, h, g, t, (uint32_t*)counts_out_dev + (size_t)i0 * words, c->stream));
+    }
+    return TFFT_OK;
+}
+
+// host buffers: a chunk of n_slots images at a time, staged in the analysis scratch behind the chunk's counts (the slots' image buffers
+// stay as they are)
+int tfft_spam_batch(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int h, int t, uint32_t* counts_out) {
+    int rc = spam_args(c, n_images, rgb, w, h, t, counts_out);
+    if (rc) return rc;
+    const size_t img_bytes = image_bytes(w, h), words = spam_words(t);
+    const int g0 = n_images < c->n_slots ? n_images : c->n_slots;
+    const size_t stage_off = ((size_t)g0 * words * sizeof(uint32_t) + 255) / 256 * 256;
+    rc = ensure_analysis(c, stage_off + (size_t)g0 * img_bytes);
+    if (rc) return rc;
+    uint32_t* cnt = (uint32_t*)c->an_buf;
+    uint8_t* stage = (uint8_t*)c->an_buf + stage_off;
+    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
+        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+        HIPCHK(c, hipMemcpyAsync(stage, rgb + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_spam(stage, w, h, g, t, cnt, c->stream));
+        HIPCHK(c, hipMemcpyAsync(counts_out + (size_t)i0 * words, cnt, (size_t)g * words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return TFFT_OK;
+}
+
 void* tfft_host_alloc(size_t bytes) {
     void* p = nullptr;
     return hipHostMalloc(&p, bytes, 0) == hipSuccess ? p : nullptr;

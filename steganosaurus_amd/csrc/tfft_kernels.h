@@ -334,4 +334,13 @@ hipError_t launch_channel_jpeg(const uint8_t* in, uint8_t* out, int W, int H, in
 hipError_t launch_robust_count(const uint8_t* raw, uint64_t n_bins, const uint8_t* header, const uint8_t* payload, uint64_t plen,
                                const int* status, int n_images, uint32_t* result, hipStream_t s);
 
+// ---- SPAM steganalysis features: counts[image][plane][dir][n^3] of the clamped difference triples, n = 2t + 1, t in 1..4
+#define TFFT_SP_COLS 256                 // pixel columns of a workgroup's tile: 768 bytes, three per thread and row
+#define TFFT_SP_ROWS 13                  // rows of the tile a workgroup counts per step; with the 3 rows of halo below them:
+#define TFFT_SP_STAGE_ROWS 16
+#define TFFT_SP_PITCH 198                // dwords per staged row: 3 (byte shift) + 3 * (3 + 256 + 3) bytes
+int spam_bands(int W, int H, int t, int n_images, int* band_rows);      // workgroups per column tile and image, and the rows each owns
+// zeroes counts (n_images * 12 n^3 words) and counts into it; n_images <= 65535
+hipError_t launch_spam(const uint8_t* rgb, int W, int H, int n_images, int t, uint32_t* counts, hipStream_t s);
+
 }  // namespace tfft

@@ -3049,6 +3049,167 @@ hipError_t launch_robust_count(const uint8_t* raw, uint64_t n_bins, const uint8_
     return hipGetLastError();
 }
 
+// ===========================================================================
+// SPAM steganalysis features: second-order co-occurrences of clamped pixel differences
+// ===========================================================================
+// For every pixel p of a plane and each of the directions d = (dy, dx) = (0,1), (1,0), (1,1), (1,-1) with p + 3d inside the image:
+//   e_k = clamp(I[p + (k-1)d] - I[p + kd], -T, T), k = 1..3;   counts[image][plane][dir][((e1+T) n + (e2+T)) n + (e3+T)] += 1,  n = 2T + 1.
+// A workgroup owns TFFT_SP_COLS pixel columns of a band of rows, all three planes, and walks the band TFFT_SP_ROWS rows at a time: the rows and
+// their halo (3 rows below, 3 pixels left and right) are staged in LDS dword for dword as they lie in memory (rows are 3*W bytes apart, so
+// every row has its own byte shift; a dword that straddles the end of what the tile needs is read byte by byte -- nothing outside the tile's own
+// bytes, all of them inside the image, is touched).  A thread then takes bytes tid, tid + 256, tid + 512 of each row of the tile (the planes
+// (tid + k) mod 3): 13 LDS bytes and four triples per byte.
+// Histograms: [3][4][n^3] words in LDS, two copies: measured on 32 x 1080p, four copies (two workgroups per CU) cost 0.83 ms, two (three
+// workgroups) 0.65, one (five) 0.69 -- the kernel waits on LDS latency more than on contention.  What contention costs
+// is equal indices inside ONE ds_add_u32 -- the LDS takes a wave's atomic apart by address -- so the copy is chosen by lane (tid mod
+// copies; the copies lie 12 n^3 words apart, in different banks), not by wave: lanes that meet on an index are spread over the copies
+// (5 % faster than per-wave copies at four copies).  The index every flat or smooth region hits,
+// (0, 0, 0), is not sent to LDS at all: a thread counts it in registers (a compare and an add per value, no scalar instruction, no atomic)
+// and adds its twelve counters once at the end, so a flat image costs no contended atomic.  A block adds its non-zero counters to the
+// zeroed result with one integer atomic each (integers: no order effects, repeated calls return identical bytes).
+#ifndef TFFT_SP_COPY_BY_LANE
+#define TFFT_SP_COPY_BY_LANE 1           // 0: one copy per wave (A/B builds only, `make variant`)
+#endif
+#ifndef TFFT_SP_COPIES
+#define TFFT_SP_COPIES 2                 // histogram copies of a workgroup (a power of two; A/B builds: 1, 4 -- T = 4 takes at most two)
+#endif
+//   grid (ceil(W/TFFT_SP_COLS), bands, n_images)  block 256   LDS tile + copies * 12 n^3 words
+template <int T>
+__device__ __forceinline__ int spam_index(int p0, int p1, int p2, int p3) {
+    constexpr int N = 2 * T + 1;
+    auto cl = [](int v) { return (v < -T ? -T : (v > T ? T : v)) + T; };
+    return (cl(p0 - p1) * N + cl(p1 - p2)) * N + cl(p2 - p3);
+}
+template <int T>
+__global__ void __launch_bounds__(256) k_spam(const uint8_t* __restrict__ rgb, int W, int H, int band_rows, int copies, uint32_t* __restrict__ counts) {
+    constexpr int N = 2 * T + 1, N3 = N * N * N, HL = 12 * N3, CENTRE = (T * N + T) * N + T;
+    constexpr int ND = TFFT_SP_PITCH;                                         // dwords a row of the tile can touch: 3 + 3*(COLS + 6) bytes
+    uint32_t* tile = reinterpret_cast<uint32_t*>(tfft_smem);                  // [TFFT_SP_STAGE_ROWS][TFFT_SP_PITCH]; byte 9 + shift of a row = pixel x0
+    uint8_t* tb = reinterpret_cast<uint8_t*>(tile);
+    unsigned* hist = reinterpret_cast<unsigned*>(tile + TFFT_SP_STAGE_ROWS * TFFT_SP_PITCH);      // [copies][3][4][N3]
+    const int tid = threadIdx.x;
+    for (int i = tid; i < copies * HL; i += 256) hist[i] = 0;
+    unsigned* h = hist + (int)((unsigned)(TFFT_SP_COPY_BY_LANE ? tid : tid >> 6) % (unsigned)copies) * HL;
+    const int x0 = blockIdx.x * TFFT_SP_COLS, yb = blockIdx.y * band_rows;
+    const int ye = yb + band_rows < H ? yb + band_rows : H;
+    const int ncols = W - x0 < TFFT_SP_COLS ? W - x0 : TFFT_SP_COLS;                    // own pixel columns
+    const int lcols = W - x0 < TFFT_SP_COLS + 3 ? W - x0 : TFFT_SP_COLS + 3;            // with the halo to the right
+    const int vlo = x0 ? 0 : 9, vhi = 9 + 3 * lcols;                                    // the tile's bytes that exist, counted from pixel x0 - 3
+    const uint8_t* img = rgb + (size_t)blockIdx.z * (size_t)W * (size_t)H * 3;
+    const unsigned row_step = (3u * (unsigned)W) & 3u;
+    unsigned cz[3][4];
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+        for (int d = 0; d < 4; d++) cz[k][d] = 0;
+    for (int yc = yb; yc < ye; yc += TFFT_SP_ROWS) {
+        const int own = ye - yc < TFFT_SP_ROWS ? ye - yc : TFFT_SP_ROWS;
+        const int staged = H - yc < own + 3 ? H - yc : own + 3;
+        const uint8_t* row0 = img + ((size_t)yc * W + x0) * 3;                          // pixel (yc, x0)
+        const unsigned s0 = (unsigned)(((uintptr_t)row0 - 9) & 3);                      // byte shift of the first staged row
+        __syncthreads();                                                                // the zeroing; the readers of the last chunk
+        for (int e = tid; e < staged * ND; e += 256) {
+            const int r = e / ND, d = e - r * ND;
+            const uint8_t* row = row0 + (size_t)r * W * 3;
+            const int sh = (int)((s0 + (unsigned)r * row_step) & 3u), lo = 4 * d - sh;  // the dword holds the tile's bytes lo .. lo+3 of the row
+            if (lo >= vlo && lo + 4 <= vhi) tile[r * TFFT_SP_PITCH + d] = *reinterpret_cast<const uint32_t*>(row + (lo - 9));
+            else
+                for (int t = 0; t < 4; t++)
+                    if (lo + t >= vlo && lo + t < vhi) tb[4 * (r * TFFT_SP_PITCH + d) + t] = row[lo + t - 9];
+        }
+        __syncthreads();
+        for (int r = 0; r < own; r++) {
+            const bool down = yc + r + 3 < H;
+            int o[4];                                                                   // LDS byte of pixel x0, plane 0 in rows r .. r+3
+#pragma unroll
+            for (int q = 0; q < 4; q++) o[q] = 4 * (r + q) * TFFT_SP_PITCH + (int)((s0 + (unsigned)(r + q) * row_step) & 3u) + 9;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const int b = tid + 256 * k, j = b / 3;
+                if (j >= ncols) continue;
+                // what lies beside or below the image is read from the tile all the same (stale bytes, inside the tile) and not counted
+                const bool right = x0 + j + 3 < W, left = x0 + j >= 3;
+                const int p0 = tb[o[0] + b];
+                const int i0 = spam_index<T>(p0, tb[o[0] + b + 3], tb[o[0] + b + 6], tb[o[0] + b + 9]);
+                const int i1 = spam_index<T>(p0, tb[o[1] + b], tb[o[2] + b], tb[o[3] + b]);
+                const int i2 = spam_index<T>(p0, tb[o[1] + b + 3], tb[o[2] + b + 6], tb[o[3] + b + 9]);
+                const int i3 = spam_index<T>(p0, tb[o[1] + b - 3], tb[o[2] + b - 6], tb[o[3] + b - 9]);
+                const bool ok0 = right, ok1 = down, ok2 = down && right, ok3 = down && left;
+                unsigned* hp = h + (b - 3 * j) * 4 * N3;
+                cz[k][0] += (ok0 && i0 == CENTRE) ? 1u : 0u;
+                cz[k][1] += (ok1 && i1 == CENTRE) ? 1u : 0u;
+                cz[k][2] += (ok2 && i2 == CENTRE) ? 1u : 0u;
+                cz[k][3] += (ok3 && i3 == CENTRE) ? 1u : 0u;
+                if (ok0 && i0 != CENTRE) atomicAdd(&hp[0 * N3 + i0], 1u);
+                if (ok1 && i1 != CENTRE) atomicAdd(&hp[1 * N3 + i1], 1u);
+                if (ok2 && i2 != CENTRE) atomicAdd(&hp[2 * N3 + i2], 1u);
+                if (ok3 && i3 != CENTRE) atomicAdd(&hp[3 * N3 + i3], 1u);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const int plane = (tid + 256 * k) % 3;
+#pragma unroll
+        for (int d = 0; d < 4; d++)
+            if (cz[k][d]) atomicAdd(&h[(plane * 4 + d) * N3 + CENTRE], cz[k][d]);
+    }
+    __syncthreads();
+    uint32_t* out = counts + (size_t)blockIdx.z * HL;
+    for (int i = tid; i < HL; i += 256) {
+        unsigned s = 0;
+        for (int c = 0; c < copies; c++) s += hist[c * HL + i];
+        if (s) atomicAdd(&out[i], s);
+    }
+}
+
+int spam_bands(int W, int H, int t, int n_images, int* band_rows) {
+    // rows of a band: a block's flush (12 n^3 atomics of 4 bytes) costs at most about an eighth of its reads (3 * TFFT_SP_COLS bytes per row),
+    // the k_phase_hist rule; fewer rows where that leaves a launch under ~1024 blocks
+    const int n = 2 * t + 1, n3 = n * n * n;
+    const int tx = (W + TFFT_SP_COLS - 1) / TFFT_SP_COLS;
+    int rows = (8 * 4 * 12 * n3 + 3 * TFFT_SP_COLS - 1) / (3 * TFFT_SP_COLS);
+    rows = (rows + TFFT_SP_ROWS - 1) / TFFT_SP_ROWS * TFFT_SP_ROWS;
+    int nb = (H + rows - 1) / rows;
+    const int fill = (1024 + tx * n_images - 1) / (tx * n_images);
+    if (nb < fill) nb = fill;
+    const int most = (H + TFFT_SP_ROWS - 1) / TFFT_SP_ROWS;
+    if (nb > most) nb = most;
+    if (nb > 65535) nb = 65535;
+    rows = ((H + nb - 1) / nb + TFFT_SP_ROWS - 1) / TFFT_SP_ROWS * TFFT_SP_ROWS;
+    *band_rows = rows;
+    return (H + rows - 1) / rows;
+}
+
+template <int T>
+static hipError_t launch_spam_t(const uint8_t* rgb, int W, int H, int n_images, uint32_t* counts, hipStream_t s) {
+    constexpr int N = 2 * T + 1, HL = 12 * N * N * N;
+    constexpr int copies = (T <= 3 || TFFT_SP_COPIES < 2) ? TFFT_SP_COPIES : 2;      // T = 4: four copies (140 KB) and the tile do not fit
+    constexpr size_t lds = (size_t)TFFT_SP_STAGE_ROWS * TFFT_SP_PITCH * 4 + (size_t)copies * HL * sizeof(unsigned);
+    int band_rows = 0;
+    const int nb = spam_bands(W, H, T, n_images, &band_rows);
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)k_spam<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_spam<T>, dim3((unsigned)((W + TFFT_SP_COLS - 1) / TFFT_SP_COLS), (unsigned)nb, (unsigned)n_images), dim3(256), lds, s, rgb, W, H,
+                       band_rows, copies, counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_spam(const uint8_t* rgb, int W, int H, int n_images, int t, uint32_t* counts, hipStream_t s) {
+    if (W < 1 || H < 1 || n_images < 1 || n_images > 65535 || t < 1 || t > 4) return hipErrorInvalidValue;
+    const int n = 2 * t + 1;
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)n_images * 12 * n * n * n * sizeof(uint32_t), s);      // every entry is written
+    if (e != hipSuccess) return e;
+    switch (t) {
+        case 1: return launch_spam_t<1>(rgb, W, H, n_images, counts, s);
+        case 2: return launch_spam_t<2>(rgb, W, H, n_images, counts, s);
+        case 3: return launch_spam_t<3>(rgb, W, H, n_images, counts, s);
+        default: return launch_spam_t<4>(rgb, W, H, n_images, counts, s);
+    }
+}
+
 }  // namespace tfft
 
 // tfft_stats.hip is a unit of its own: hipcc compiles it apart (csrc/Makefile), and so does the CPU emulation of the tests

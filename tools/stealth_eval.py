@@ -18,7 +18,15 @@
           channel kernels alone, the robustness call with one channel and with all of them, against tfft_extract_stream_batch_dev on the
           same batch.
 
+  --spam  the blind detector on synthetic covers (synth.cover_rgb, NOT photographs): per payload N covers of
+          1920 x 1080 and their one-shot stego (default alpha 0.5 and density 0.7, one shared walk), payloads of 4096, 512 and 64 bytes
+          (--payload, a comma list).  Per image the SPAM-686 features of tfft_spam_batch_dev (analysis.spam_features, mean over the planes);
+          a Fisher linear discriminant (analysis.fld_fit) fitted on one half of the images and scored on the other, then the halves
+          swapped: both AUCs, beside the KL and +-alpha-mass AUCs of --auc for the same images.
+          --cost also times tfft_spam_batch_dev (T = 3) on the same batches.
+
     python tools/stealth_eval.py --cost [--rounds 5 --steps 5]
+    python tools/stealth_eval.py --spam [--n 512 --n-ref 64 --payload 4096,512,64]
     python tools/stealth_eval.py --robust [--rounds 5 --steps 5]
     python tools/stealth_eval.py --auc [--n 256 --n-ref 64 --payload 4096] [--out FILE.json]
 One JSON line on stdout (and in --out)."""
@@ -62,6 +70,7 @@ def cost(name, rounds, steps, warmup):
     dev = "cuda:0"
     covers = torch.from_numpy(np.stack([cover_rgb(w, h, i) if i % 2 else gradient_cover(w, h, i) for i in range(nimg)])).to(dev)
     other = torch.clamp(covers.to(torch.int16) + torch.randint(-2, 3, covers.shape, dtype=torch.int16, device=dev), 0, 255).to(torch.uint8)
+    flat = torch.full_like(covers, 97)
     d_bins = torch.from_numpy(sbins.view(np.uint8).reshape(-1, 8).copy()).to(dev)
     hist = torch.empty(nimg * 3 * NBINS, dtype=torch.int32, device=dev)
     sse = torch.empty(nimg * 3, dtype=torch.int64, device=dev)
@@ -69,6 +78,7 @@ def cost(name, rounds, steps, warmup):
     d_hdr = torch.empty(nimg * 38, dtype=torch.uint8, device=dev)
     d_pay = torch.empty(nimg * PLEN, dtype=torch.uint8, device=dev)
     d_st = torch.empty(nimg, dtype=torch.int32, device=dev)
+    spam = torch.empty(nimg * 3 * 4 * 343, dtype=torch.int32, device=dev)
     torch.cuda.synchronize()
     ctx = B.Context(w, h, slots=slots)
     ctx.set_bit_index(idx)
@@ -79,6 +89,8 @@ def cost(name, rounds, steps, warmup):
         "phase_hist": lambda: ctx.phase_hist_batch_dev(nimg, covers.data_ptr(), w, h, hist.data_ptr(), nbins=NBINS, center=center),
         "quality": lambda: ctx.quality_batch_dev(nimg, covers.data_ptr(), other.data_ptr(), w, h, sse.data_ptr(), ssim.data_ptr()),
         "quality_sse_only": lambda: ctx.quality_batch_dev(nimg, covers.data_ptr(), other.data_ptr(), w, h, sse.data_ptr(), None),
+        "spam": lambda: ctx.spam_batch_dev(nimg, covers.data_ptr(), w, h, spam.data_ptr(), t=3),
+        "spam_flat": lambda: ctx.spam_batch_dev(nimg, flat.data_ptr(), w, h, spam.data_ptr(), t=3),
     }
     ms = {leg: [] for leg in legs}
     for _ in range(rounds):
@@ -96,6 +108,7 @@ def cost(name, rounds, steps, warmup):
     base = out["extract_stream"]["ms_per_call"]
     for leg in legs:
         out[leg]["vs_extract"] = round(out[leg]["ms_per_call"] / base, 4)
+    out["spam"]["vs_quality_sse_only"] = round(out["spam"]["ms_per_call"] / out["quality_sse_only"]["ms_per_call"], 4)
     return {"image": [w, h], "images_per_call": nimg, "slots": slots, "center": center, "legs": out}
 
 
@@ -177,6 +190,77 @@ def auc_cells(n, n_ref, chunk, seed0, plen=PLEN):
             res[key]["fit_not_converged"] = int(sum(1 for v in iters[cell] if v < 0))
     return {"image": [w, h], "covers": "synth.cover_rgb (synthetic, not photographs)", "payload_bytes": plen, "n_bins": NBINS,
             "n_ref": n_ref, "cells": res}
+
+
+def spam_cells(n, n_ref, chunk, seed0, payloads):
+    """per payload: AUC of SPAM-686 + FLD (two folds) beside the white-box KL and +-alpha-mass AUCs, same covers and stegos"""
+    import torch
+    from steganosaurus_amd import analysis as A
+    from steganosaurus_amd import binding as B
+    from steganosaurus_amd.synth import cover_rgb
+    w, h, alpha = 1920, 1080, 0.5
+    ph, pw = next_pow2(h), next_pow2(w)
+    dev = "cuda:0"
+    ctx = B.Context(w, h, slots=chunk)
+    rng = np.random.default_rng(seed0)
+    streams = {}
+    for plen in payloads:
+        n_bins = 912 + 56 * plen
+        bins = B.Walk(bytes(range(32)), ph, pw).next(n_bins)
+        streams[plen] = (n_bins, torch.from_numpy(bins.view(np.uint8).reshape(-1, 8).copy()).to(dev),
+                         torch.from_numpy(np.tile(header(plen), chunk)).to(dev),
+                         torch.from_numpy(rng.integers(0, 256, chunk * plen).astype(np.uint8)).to(dev))
+
+    def hists(batch):
+        out = torch.empty(len(batch) * 3 * NBINS, dtype=torch.int32, device=dev)
+        ctx.phase_hist_batch_dev(len(batch), batch.data_ptr(), w, h, out.data_ptr(), nbins=NBINS)
+        ctx.sync()
+        return out.cpu().numpy().view(np.uint32).reshape(len(batch), 3, NBINS).astype(np.int64)
+
+    def feats(batch):
+        out = torch.empty(len(batch) * 3 * 4 * 343, dtype=torch.int32, device=dev)
+        ctx.spam_batch_dev(len(batch), batch.data_ptr(), w, h, out.data_ptr(), t=3)
+        ctx.sync()
+        counts = out.cpu().numpy().view(np.uint32).reshape(len(batch), 3, 4, 343)
+        return A.spam_features(counts).mean(axis=1)                 # the per-image feature: the mean over the planes
+
+    ref = np.zeros((3, NBINS), np.int64)
+    for i0 in range(0, n_ref, chunk):
+        covers = torch.from_numpy(np.stack([cover_rgb(w, h, 100000 + i) for i in range(i0, min(n_ref, i0 + chunk))])).to(dev)
+        ref += hists(covers).sum(axis=0)
+    cover_h, cover_f = [], []
+    stego_h = {p: [] for p in payloads}
+    stego_f = {p: [] for p in payloads}
+    for i0 in range(0, n, chunk):
+        g = min(n, i0 + chunk) - i0
+        covers = torch.from_numpy(np.stack([cover_rgb(w, h, seed0 + i) for i in range(i0, i0 + g)])).to(dev)
+        cover_h.append(hists(covers))
+        cover_f.append(feats(covers))
+        for plen in payloads:
+            n_bins, d_bins, d_hdr, d_pay = streams[plen]
+            stego = torch.empty_like(covers)
+            ctx.embed_stream_batch_dev(g, covers.data_ptr(), w, h, d_bins.data_ptr(), n_bins, d_hdr.data_ptr(), d_pay.data_ptr(), plen,
+                                       stego.data_ptr(), alpha=alpha)
+            stego_h[plen].append(hists(stego))
+            stego_f[plen].append(feats(stego))
+            del stego
+    ctx.close()
+    cover_h, cover_f = np.concatenate(cover_h), np.concatenate(cover_f)
+    half = n // 2
+    res = {}
+    for plen in payloads:
+        sh, sf = np.concatenate(stego_h[plen]), np.concatenate(stego_f[plen])
+        folds = []
+        for (fit, test) in ((slice(0, half), slice(half, n)), (slice(half, n), slice(0, half))):
+            model = A.fld_fit(sf[fit], cover_f[fit])
+            folds.append(round(A.auc(A.fld_score(sf[test], model), A.fld_score(cover_f[test], model)), 4))
+        kl_pos, kl_neg = A.kl_divergence(sh, ref).sum(axis=1), A.kl_divergence(cover_h, ref).sum(axis=1)
+        pm_pos, pm_neg = A.peak_mass(sh, alpha).sum(axis=1), A.peak_mass(cover_h, alpha).sum(axis=1)
+        res["payload_%d" % (plen - 16)] = {"payload_bytes": plen - 16, "stream_bits": 912 + 56 * plen, "n": int(n),
+                                           "auc_spam_fld_folds": folds, "auc_kl": round(A.auc(kl_pos, kl_neg), 4),
+                                           "auc_peak": round(A.auc(pm_pos, pm_neg), 4)}
+    return {"image": [w, h], "covers": "synth.cover_rgb (synthetic, not photographs)", "alpha": alpha, "density": 0.7, "features": "SPAM-686, T = 3",
+            "classifier": "Fisher linear discriminant, ridge 1e-3, fitted on one half and scored on the other", "n_ref": n_ref, "cells": res}
 
 
 def robust(rounds, steps, warmup, plen=PLEN):
@@ -261,7 +345,9 @@ def main():
     ap.add_argument("--n-ref", type=int, default=64)
     ap.add_argument("--chunk", type=int, default=32)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--payload", type=int, default=4096, help="--auc: ciphertext bytes per image (the tag adds 16)")
+    ap.add_argument("--spam", action="store_true")
+    ap.add_argument("--payload", default=None, help="ciphertext bytes per image (the tag adds 16): --auc one value (default 4096), "
+                                                    "--spam a comma list (default 4096,512,64)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -271,7 +357,9 @@ def main():
     if a.cost:
         res["cost"] = {wl: cost(wl, a.rounds, a.steps, a.warmup) for wl in a.workloads.split(",")}
     if a.auc:
-        res["auc"] = auc_cells(a.n, a.n_ref, a.chunk, a.seed, a.payload + 16)
+        res["auc"] = auc_cells(a.n, a.n_ref, a.chunk, a.seed, int(a.payload or 4096) + 16)
+    if a.spam:
+        res["spam"] = spam_cells(a.n, a.n_ref, a.chunk, a.seed, [int(v) + 16 for v in (a.payload or "4096,512,64").split(",")])
     if a.robust:
         res["robust"] = robust(a.rounds, a.steps, a.warmup)
     line = json.dumps(res)
