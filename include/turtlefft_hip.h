@@ -373,9 +373,9 @@ int tfft_channel_batch(tfft_ctx* ctx, int n_images, const uint8_t* rgb, int w, i
  *      (38 bytes per image) and payload (payload_len bytes per image): a decode at the KNOWN length, so the error rate after the
  *      repetition code stays measurable when the header is lost.
  * n_bins >= 912 + 56*payload_len and n_channels >= 1, else TFFT_E_INVALID; otherwise the errors of the calls above.  Works chunk by chunk
- * (n_slots images, every channel in turn) and keeps one attacked copy of a chunk in a scratch buffer grown on demand; stego_dev is never
+ * (n_slots images, every channel in turn) and keeps one attacked copy of a chunk in the analysis scratch (grown on demand); stego_dev is never
  * written.  Results do not depend on n_slots, and repeated calls return the same.  The slots are left as by an extract batch call.  The _dev
- * form does not synchronise (but for growing its scratch); the host form stages chunk by chunk like tfft_phase_hist_batch and synchronises.
+ * form does not synchronise (but for growing the scratch); the host form stages chunk by chunk like tfft_phase_hist_batch and synchronises.
  * One list for all images: there is no _walks form. */
 int tfft_robustness_batch_dev(tfft_ctx* ctx, int n_images, const void* stego_dev, int w, int h, int center,
                               const void* bins_dev, uint64_t n_bins, double alpha,

@@ -153,10 +153,10 @@ struct tfft_ctx {
     std::vector<int32_t> bx_state; int bx_last_n = 0;
     ExactWin* bx_win = nullptr; ExactCandB* bx_cand = nullptr; unsigned long long* bx_below = nullptr; unsigned* bx_n = nullptr;
     unsigned* bx_idx = nullptr; ExactGroup* bx_grp = nullptr; double2* bx_part = nullptr; ExactVal* bx_val = nullptr; size_t bx_part_cap = 0, bx_val_cap = 0;
-    // stego analysis (tfft_phase_hist_batch*, tfft_quality_batch*): per-block partials of a chunk (+ the host forms' results), grown on demand
+    // the analysis scratch (tfft_phase_hist_batch*, tfft_quality_batch*, tfft_channel_batch, tfft_robustness_batch*, tfft_spam_batch): what one
+    // chunk of the running call needs beside the slots -- partials, attacked images, decode outputs, the host forms' staged images and
+    // results.  One buffer, grown on demand (ensure_analysis), laid out afresh by every call (Carve); nothing in it outlives its call
     void* an_buf = nullptr; size_t an_cap = 0;
-    // robustness analysis (tfft_robustness_batch*): a chunk's attacked images, its decode outputs and the host form's results, grown on demand
-    void* rb_buf = nullptr; size_t rb_cap = 0;
 
     uint8_t* img(int i) const { return img_pool + (size_t)i * img_stride_b; }
     float2* spec(int i) const { return spec_pool + (size_t)i * slot_stride; }
@@ -699,7 +699,7 @@ int tfft_destroy(tfft_ctx* c) {
     (void)hipFree(c->sel); (void)hipFree(c->med); (void)hipFree(c->partial); (void)hipFree(c->amb); (void)hipFree(c->usable); (void)hipFree(c->err); (void)hipFree(c->ex_cand); (void)hipFree(c->ex_val); (void)hipFree(c->ex_below); (void)hipFree(c->ex_n); for (auto& kv : c->ex_table) (void)hipFree(kv.second); (void)hipFree(c->trash); (void)hipFree(c->bit_index); (void)hipFree(c->last_row); (void)hipFree(c->ph_jit);
     (void)hipFree(c->fit_d); (void)hipFree(c->fit_mu); (void)hipFree(c->fit_part); (void)hipFree(c->fit_cnt); (void)hipFree(c->fit_iters); (void)hipFree(c->fit_wrong);
     (void)hipFree(c->bx_win); (void)hipFree(c->bx_cand); (void)hipFree(c->bx_below); (void)hipFree(c->bx_n); (void)hipFree(c->bx_idx); (void)hipFree(c->bx_grp);
-    (void)hipFree(c->bx_part); (void)hipFree(c->bx_val); (void)hipFree(c->an_buf); (void)hipFree(c->rb_buf);
+    (void)hipFree(c->bx_part); (void)hipFree(c->bx_val); (void)hipFree(c->an_buf);
     for (auto& b : c->tb) { (void)hipFree(b.cnt); (void)hipFree(b.off); (void)hipFree(b.ent); (void)hipFree(b.fl); (void)hipFree(b.pb); (void)hipFree(b.jp); }
     for (auto& kv : c->tw) (void)hipFree(kv.second);
     for (auto& kv : c->dc) (void)hipFree(kv.second);
@@ -1932,6 +1932,33 @@ int for_chunks(tfft_ctx* c, int n_images, int w, int h, int center, bool split, 
     }
     return TFFT_OK;
 }
+// The chunk loop of the calls that need no more from a driver: at most `limit` images at a time, body(i0, g) for the images [i0, i0+g)
+template <class Body>
+int for_images(int n_images, int limit, Body&& body) {
+    for (int i0 = 0; i0 < n_images; i0 += limit) {
+        const int rc = body(i0, (n_images - i0 < limit) ? n_images - i0 : limit);
+        if (rc) return rc;
+    }
+    return TFFT_OK;
+}
+// One per-image array of a host-buffer call: image i at host + i*stride bytes, a chunk's share staged at dev.  host == nullptr: the call
+// does not use the array (a stride of 0 bytes: nothing to move)
+struct HostArray { const void* host; void* dev; size_t stride; };
+// the shares of the images [i0, i0+g) go up, in the order listed ...
+int upload(tfft_ctx* c, const std::vector<HostArray>& arrays, int i0, int g, hipStream_t st) {
+    for (const HostArray& a : arrays)
+        if (a.host && a.stride) HIPCHK(c, hipMemcpyAsync(a.dev, (const char*)a.host + (size_t)i0 * a.stride, (size_t)g * a.stride, hipMemcpyHostToDevice, st));
+    return TFFT_OK;
+}
+// ... and come down (the arrays listed here are the call's outputs: host is writable), then the stream is drained: the staging is free again
+int download_sync(tfft_ctx* c, const std::vector<HostArray>& arrays, int i0, int g, hipStream_t st) {
+    for (const HostArray& a : arrays)
+        if (a.host && a.stride) HIPCHK(c, hipMemcpyAsync((char*)const_cast<void*>(a.host) + (size_t)i0 * a.stride, a.dev, (size_t)g * a.stride, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return TFFT_OK;
+}
+// slots [0, g) lose their images: no spectrum, and no device image that tfft_lowfreq_mag could read again
+void drop_images(tfft_ctx* c, int g) { for (int i = 0; i < g; i++) { c->slots[i].has_spec = false; c->slots[i].rgb_src = nullptr; } }
 // the three device-buffer embeds: every chunk through embed_chunk
 int embed_chunks(tfft_ctx* c, int n_images, int w, int h, int center, bool split, const EmbedDev& e) {
     const size_t img_bytes = image_bytes(w, h);
@@ -1947,7 +1974,7 @@ static int batch_after(tfft_ctx* c, int n_images, int w, int h, int center) {
     const int g = n_images < c->n_slots ? n_images : c->n_slots;
     int rc = batch_geometry(c, g, w, h, center);
     if (rc) return rc;
-    for (int i = 0; i < g; i++) { c->slots[i].has_spec = false; c->slots[i].rgb_src = nullptr; }
+    drop_images(c, g);
     return TFFT_OK;
 }
 
@@ -2402,26 +2429,28 @@ int tfft_embed_stream_batch_fit_dev(tfft_ctx* c, int n_images, const void* rgb_d
     if (rc) return rc;
     const ChunkArgs a = ChunkArgs::list(bins_dev, n_bins, alpha).capacity(rmin, rmax, magmin).frames(header_dev, payload_dev, payload_len)
                             .walks(jitter_dev, adaptive);
-    const size_t img_bytes = (size_t)w * h * 3;
+    const size_t img_bytes = image_bytes(w, h);
     std::vector<int32_t> iters((size_t)c->n_slots);
     int32_t* bx = bx_begin(c, n_images, usable_out_dev);
-    // (Not for_chunks: the fit copies every chunk's covers whether or not the capacities are settled, settles against that copy, and
-    // uploads the iteration counts after the settling -- the driver would have to learn all three.)
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+    // (The plain chunk loop, not for_chunks: the fit copies every chunk's covers whether or not the capacities are settled, settles against
+    // that copy, and uploads the iteration counts after the settling -- the driver would have to learn all three.)
+    rc = for_images(n_images, c->n_slots, [&](int i0, int g) -> int {
         rc = batch_geometry(c, g, w, h, center);
         if (rc) return rc;
         // every iteration adds to the ORIGINAL covers: the chunk's own copy in the slots' image buffers (rgb_out may be rgb)
-        HIPCHK(c, hipMemcpyAsync(c->img(0), (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyDeviceToDevice, c->stream));
-        rc = fit_chunk(c, g, a.from(i0), c->img(0), usable_out_dev ? (unsigned long long*)usable_out_dev + i0 : nullptr, max_iters, margin,
-                       (uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes, iters.data(), wrong_out_dev ? (uint32_t*)wrong_out_dev + i0 : nullptr);
+        HIPCHK(c, hipMemcpyAsync(c->img(0), nth((const uint8_t*)rgb_dev, i0, img_bytes), (size_t)g * img_bytes, hipMemcpyDeviceToDevice, c->stream));
+        unsigned long long* usable = nth((unsigned long long*)usable_out_dev, i0);
+        rc = fit_chunk(c, g, a.from(i0), c->img(0), usable, max_iters, margin, nth((uint8_t*)rgb_out_dev, i0, img_bytes), iters.data(),
+                       nth((uint32_t*)wrong_out_dev, i0));
         if (rc) return rc;
-        if (bx) { rc = bx_settle(c, 0, g, c->img(0), a, (unsigned long long*)usable_out_dev + i0, bx + i0, c->stream); if (rc) return rc; }
+        if (bx) { rc = bx_settle(c, 0, g, c->img(0), a, usable, bx + i0, c->stream); if (rc) return rc; }
         if (iters_out_dev) {
             HIPCHK(c, hipMemcpyAsync((int32_t*)iters_out_dev + i0, iters.data(), (size_t)g * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));      // (the host array is reused by the next chunk)
         }
-    }
+        return TFFT_OK;
+    });
+    if (rc) return rc;
     return n_images ? check_err_flag(c) : TFFT_OK;
 }
 
@@ -2441,29 +2470,23 @@ int tfft_embed_stream_batch_fit(tfft_ctx* c, int n_images, const uint8_t* rgb, i
     // (every chunk goes through the front of the staging buffers)
     const ChunkArgs a = ChunkArgs::list(c->stage_bins, n_bins, alpha).capacity(rmin, rmax, magmin).frames(c->sio_hdr, c->sio_pay, payload_len)
                             .walks(jitter ? c->stage_jit : nullptr, adaptive);
-    const size_t img_bytes = (size_t)w * h * 3;
+    const size_t img_bytes = image_bytes(w, h);
     std::vector<int32_t> iters((size_t)c->n_slots);
     int32_t* bx = bx_begin(c, n_images, usable_out);
     hipStream_t st = c->stream;
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
+    const std::vector<HostArray> in = {{rgb, c->img(0), img_bytes}, {bins, c->stage_bins, n_bins * sizeof(tfft_bin)}, {jitter, c->stage_jit, n_bins * sizeof(float)},
+                                       {header, c->sio_hdr, kHeaderBytes}, {payload, c->sio_pay, payload_len}};
+    const std::vector<HostArray> out = {{rgb_out, c->out_pool, img_bytes}, {usable_out, c->usable, sizeof(uint64_t)}, {wrong_out, c->fit_wrong, sizeof(uint32_t)}};
+    rc = for_images(n_images, c->n_slots, [&](int i0, int g) -> int {
         rc = batch_geometry(c, g, w, h, center);
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->img(0), rgb + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->stage_bins, bins + (size_t)i0 * n_bins, (size_t)g * n_bins * sizeof(tfft_bin), hipMemcpyHostToDevice, st));
-        if (jitter) HIPCHK(c, hipMemcpyAsync(c->stage_jit, jitter + (size_t)i0 * n_bins, (size_t)g * n_bins * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->sio_hdr, header + (size_t)i0 * kHeaderBytes, (size_t)g * kHeaderBytes, hipMemcpyHostToDevice, st));
-        if (payload_len) HIPCHK(c, hipMemcpyAsync(c->sio_pay, payload + (size_t)i0 * payload_len, (size_t)g * payload_len, hipMemcpyHostToDevice, st));
-        rc = fit_chunk(c, g, a, c->img(0), usable_out ? c->usable : nullptr, max_iters, margin, c->out_pool, iters.data(), c->fit_wrong);
-        if (rc) return rc;
-        if (bx) { rc = bx_settle(c, 0, g, c->img(0), a, c->usable, bx + i0, st); if (rc) return rc; }
-        HIPCHK(c, hipMemcpyAsync(rgb_out + (size_t)i0 * img_bytes, c->out_pool, (size_t)g * img_bytes, hipMemcpyDeviceToHost, st));
-        if (usable_out) HIPCHK(c, hipMemcpyAsync(usable_out + i0, c->usable, (size_t)g * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        if (wrong_out) HIPCHK(c, hipMemcpyAsync(wrong_out + i0, c->fit_wrong, (size_t)g * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (iters_out) memcpy(iters_out + i0, iters.data(), (size_t)g * sizeof(int32_t));
-    }
-    return check_err_flag(c);
+        if (!rc) rc = upload(c, in, i0, g, st);
+        if (!rc) rc = fit_chunk(c, g, a, c->img(0), usable_out ? c->usable : nullptr, max_iters, margin, c->out_pool, iters.data(), c->fit_wrong);
+        if (!rc && bx) rc = bx_settle(c, 0, g, c->img(0), a, c->usable, bx + i0, st);
+        if (!rc) rc = download_sync(c, out, i0, g, st);
+        if (!rc && iters_out) memcpy(iters_out + i0, iters.data(), (size_t)g * sizeof(int32_t));
+        return rc;
+    });
+    return rc ? rc : check_err_flag(c);
 }
 
 int tfft_lowfreq_mag_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, int h, int center, int region, void* out_dev) {
@@ -2476,30 +2499,43 @@ int tfft_lowfreq_mag_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, i
     // the row sums of image k of a chunk in tmp(k), as tfft_lowfreq_mag keeps them (free outside a call: nothing lives there between calls)
     const size_t row_bytes = (size_t)s.H * 3 * region * sizeof(double2), out_len = (size_t)3 * region * region;
     if (row_bytes > c->slot_stride * sizeof(float2)) return TFFT_E_INVALID;
-    const size_t img_bytes = (size_t)w * h * 3;
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
-        HIPCHK(c, launch_lowfreq_f64_batch((const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, s.W, s.H, s.PW, s.PH, s.center, region, g,
-                                           (double2*)c->tmp(0), c->slot_stride * sizeof(float2) / sizeof(double2), (double*)out_dev + (size_t)i0 * out_len,
-                                           c->stream));
-    }
-    return TFFT_OK;
+    const size_t img_bytes = image_bytes(w, h);
+    return for_images(n_images, c->n_slots, [&](int i0, int g) -> int {
+        HIPCHK(c, launch_lowfreq_f64_batch(nth((const uint8_t*)rgb_dev, i0, img_bytes), s.W, s.H, s.PW, s.PH, s.center, region, g, (double2*)c->tmp(0),
+                                           c->slot_stride * sizeof(float2) / sizeof(double2), nth((double*)out_dev, i0, out_len), c->stream));
+        return TFFT_OK;
+    });
 }
 
 // ---- stego analysis: annulus phase histograms, cover / stego quality
 }  // extern "C"
 namespace {
-// the analysis scratch (partials of one chunk, then the host forms' results): grown on demand; an earlier call may still read it.
-// (Like bx_value_buffers, no quiesce(): the analysis calls run on the context's stream alone and are never captured.)
+// The analysis scratch, shared by the analysis, robustness and SPAM calls (no call keeps anything in it for the next): grown on demand; an
+// earlier call may still read it, so the stream is drained before the old buffer goes.  The replaced buffer leaves tfft_device_bytes.
+// (Like bx_value_buffers, no quiesce(): these calls run on the context's stream alone and are never captured.)
 int ensure_analysis(tfft_ctx* c, size_t bytes) {
     if (c->an_buf && bytes <= c->an_cap) return TFFT_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->an_buf); c->an_buf = nullptr; c->an_cap = 0;
+    (void)hipFree(c->an_buf); c->an_buf = nullptr; c->dev_bytes -= c->an_cap; c->an_cap = 0;
     const size_t cap = grown(bytes, 4096);
     int rc = dev_alloc(c, &c->an_buf, cap);
     if (rc) return rc;
     c->an_cap = cap;
     return TFFT_OK;
+}
+// Typed arrays taken off a base pointer one behind the other, each at a multiple of 256 bytes; off a null base the takes only add up
+struct Carve {
+    char* base; size_t end = 0;
+    template <class T> T* take(size_t n) { const size_t at = (end + 255) / 256 * 256; end = at + n * sizeof(T); return base ? (T*)(base + at) : nullptr; }
+};
+// A call's layout of the scratch, run twice: off a null base for the bytes to ensure, then off the buffer (size and layout cannot drift apart)
+template <class Layout> int carve_analysis(tfft_ctx* c, Layout&& layout) {
+    Carve size{nullptr};
+    layout(size);
+    const int rc = ensure_analysis(c, size.end);
+    Carve k{(char*)c->an_buf};
+    if (!rc) layout(k);
+    return rc;
 }
 
 int phase_hist_args(tfft_ctx* c, int n_images, const void* rgb, int w, int h, int center, int n_hist_bins, const void* out, int* log_bins) {
@@ -2511,24 +2547,27 @@ int phase_hist_args(tfft_ctx* c, int n_images, const void* rgb, int w, int h, in
     return TFFT_OK;
 }
 
-// g images (device, packed) -> storing forward into slots [0, g) -> histograms to hist (device, 3*nbins words per image); extra: bytes
-// of the scratch the caller keeps after the partials
+// g images (device, packed) -> storing forward into slots [0, g) -> histograms, 3*nbins words per image, to hist (device); or, with host
+// given, staged in the scratch behind the partials and copied to images [i0, i0+g) of that host array, which synchronises
 int phase_hist_chunk(tfft_ctx* c, int g, const uint8_t* rgb, int w, int h, int center, double rmin, double rmax, const double thr[3], int log_bins,
-                     size_t extra, uint32_t** hist) {
+                     uint32_t* hist, uint32_t* host = nullptr, int i0 = 0) {
     int rc = batch_geometry(c, g, w, h, center);
     if (rc) return rc;
     PhaseHistParams P{};
     P.cap = cap_params(c, c->slots[0], rmin, rmax);
     for (int q = 0; q < 3; q++) P.t2[q] = thr ? mag2_threshold(thr[q]) : -INFINITY;
     P.log_bins = log_bins;
-    const size_t part = ((size_t)g * 3 * phase_hist_blocks(P.cap, log_bins, g) << log_bins) * sizeof(unsigned);
-    rc = ensure_analysis(c, part + extra);
+    const size_t words = (size_t)3 << log_bins;
+    unsigned* part = nullptr;
+    rc = carve_analysis(c, [&](Carve& k) {
+        part = k.take<unsigned>((size_t)g * phase_hist_blocks(P.cap, log_bins, g) * words);
+        if (host) hist = k.take<uint32_t>((size_t)g * words);
+    });
     if (rc) return rc;
-    if (!*hist) *hist = (uint32_t*)((char*)c->an_buf + part);
     rc = enqueue_forward(c, 0, g, rgb, c->stream);      // the storing forward: complex values are needed, not |F|^2
     if (rc) return rc;
-    HIPCHK(c, launch_phase_hist(c->spec(0), P, g, (unsigned*)c->an_buf, *hist, c->stream));
-    return TFFT_OK;
+    HIPCHK(c, launch_phase_hist(c->spec(0), P, g, part, hist, c->stream));
+    return host ? download_sync(c, {{host, hist, words * sizeof(uint32_t)}}, i0, g, c->stream) : TFFT_OK;
 }
 
 int quality_args(const tfft_ctx* c, int n_images, const void* a, const void* b, int w, int h, const void* sse, const void* ssim) {
@@ -2546,21 +2585,9 @@ QualityParams quality_params(int w, int h) {
     for (int k = 0; k < 11; k++) P.g[k] = (float)(g[k] / sum);
     return P;
 }
+// the partials of each kind (SSE, SSIM) of the call's largest chunk: one per (image, plane, tile)
+size_t quality_tiles(const tfft_ctx* c, int n_images, int w, int h) { return (size_t)(n_images < c->n_slots ? n_images : c->n_slots) * 3 * quality_partials(w, h); }
 
-// the partials of a chunk of g pairs, at the start of the analysis scratch (SSE then SSIM per (image, plane, tile))
-size_t quality_part_bytes(int g, const QualityParams& P) {
-    return (size_t)g * 3 * quality_partials(P.W, P.H) * (sizeof(unsigned long long) + sizeof(double));
-}
-
-// g image pairs (device, packed) -> sse / ssim (device, 3 per image; ssim may be nullptr).  The caller has sized the scratch
-// (ensure_analysis of at least quality_part_bytes(g, P))
-int quality_chunk(tfft_ctx* c, int g, const uint8_t* a, const uint8_t* b, const QualityParams& P, unsigned long long* sse, double* ssim) {
-    const size_t nt = (size_t)g * 3 * quality_partials(P.W, P.H);
-    unsigned long long* sse_part = (unsigned long long*)c->an_buf;
-    double* ssim_part = (double*)(sse_part + nt);
-    HIPCHK(c, launch_quality(a, b, P, g, sse_part, ssim_part, sse, ssim, c->stream));
-    return TFFT_OK;
-}
 }  // namespace
 extern "C" {
 
@@ -2569,14 +2596,10 @@ int tfft_phase_hist_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, in
     int lb = 0;
     int rc = phase_hist_args(c, n_images, rgb_dev, w, h, center, n_hist_bins, hist_out_dev, &lb);
     if (rc) return rc;
-    const size_t img_bytes = (size_t)w * h * 3, hist_len = (size_t)3 << lb;
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
-        uint32_t* hist = (uint32_t*)hist_out_dev + (size_t)i0 * hist_len;
-        rc = phase_hist_chunk(c, g, (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, w, h, center, rmin, rmax, thr, lb, 0, &hist);
-        if (rc) return rc;
-    }
-    return TFFT_OK;
+    const size_t img_bytes = image_bytes(w, h), hist_len = (size_t)3 << lb;
+    return for_images(n_images, c->n_slots, [&](int i0, int g) {
+        return phase_hist_chunk(c, g, nth((const uint8_t*)rgb_dev, i0, img_bytes), w, h, center, rmin, rmax, thr, lb, nth((uint32_t*)hist_out_dev, i0, hist_len));
+    });
 }
 
 int tfft_phase_hist_batch(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int h, int center, double rmin, double rmax,
@@ -2584,34 +2607,27 @@ int tfft_phase_hist_batch(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, 
     int lb = 0;
     int rc = phase_hist_args(c, n_images, rgb, w, h, center, n_hist_bins, hist_out, &lb);
     if (rc) return rc;
-    const size_t img_bytes = (size_t)w * h * 3, hist_len = (size_t)3 << lb;
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
-        for (int i = 0; i < g; i++) { c->slots[i].has_spec = false; c->slots[i].rgb_src = nullptr; }      // their images go now (the forward follows)
-        HIPCHK(c, hipMemcpyAsync(c->img(0), rgb + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, c->stream));
-        uint32_t* hist = nullptr;
-        rc = phase_hist_chunk(c, g, c->img(0), w, h, center, rmin, rmax, thr, lb, (size_t)g * hist_len * sizeof(uint32_t), &hist);
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(hist_out + (size_t)i0 * hist_len, hist, (size_t)g * hist_len * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return TFFT_OK;
+    return for_images(n_images, c->n_slots, [&](int i0, int g) {
+        drop_images(c, g);      // their images go now (the forward follows)
+        rc = upload(c, {{rgb, c->img(0), image_bytes(w, h)}}, i0, g, c->stream);
+        return rc ? rc : phase_hist_chunk(c, g, c->img(0), w, h, center, rmin, rmax, thr, lb, nullptr, hist_out, i0);
+    });
 }
 
 int tfft_quality_batch_dev(tfft_ctx* c, int n_images, const void* a_dev, const void* b_dev, int w, int h, void* sse_out_dev, void* ssim_out_dev) {
     int rc = quality_args(c, n_images, a_dev, b_dev, w, h, sse_out_dev, ssim_out_dev);
     if (rc) return rc;
     const QualityParams P = quality_params(w, h);
-    const size_t img_bytes = (size_t)w * h * 3;
-    rc = ensure_analysis(c, quality_part_bytes(n_images < c->n_slots ? n_images : c->n_slots, P));
+    const size_t img_bytes = image_bytes(w, h), nt = quality_tiles(c, n_images, w, h);
+    unsigned long long* sse_part = nullptr;
+    double* ssim_part = nullptr;
+    rc = carve_analysis(c, [&](Carve& k) { sse_part = k.take<unsigned long long>(nt); ssim_part = k.take<double>(nt); });
     if (rc) return rc;
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
-        rc = quality_chunk(c, g, (const uint8_t*)a_dev + (size_t)i0 * img_bytes, (const uint8_t*)b_dev + (size_t)i0 * img_bytes, P,
-                           (unsigned long long*)sse_out_dev + (size_t)i0 * 3, ssim_out_dev ? (double*)ssim_out_dev + (size_t)i0 * 3 : nullptr);
-        if (rc) return rc;
-    }
-    return TFFT_OK;
+    return for_images(n_images, c->n_slots, [&](int i0, int g) -> int {
+        HIPCHK(c, launch_quality(nth((const uint8_t*)a_dev, i0, img_bytes), nth((const uint8_t*)b_dev, i0, img_bytes), P, g, sse_part, ssim_part,
+                                 nth((unsigned long long*)sse_out_dev, i0, 3), nth((double*)ssim_out_dev, i0, 3), c->stream));
+        return TFFT_OK;
+    });
 }
 
 // host buffers: a chunk of n_slots pairs at a time, staged OUTSIDE the slots' image buffers (which tfft_lowfreq_mag and the exact statistics
@@ -2623,26 +2639,23 @@ int tfft_quality_batch(tfft_ctx* c, int n_images, const uint8_t* a, const uint8_
     rc = pipe_init(c);
     if (rc) return rc;
     const QualityParams P = quality_params(w, h);
-    const size_t img_bytes = (size_t)w * h * 3;
-    const int g0 = n_images < c->n_slots ? n_images : c->n_slots;
-    const size_t part = quality_part_bytes(g0, P), res = (size_t)g0 * 3 * (sizeof(unsigned long long) + sizeof(double));
-    const size_t stage_off = (part + res + 255) / 256 * 256;
-    rc = ensure_analysis(c, stage_off + (size_t)g0 * img_bytes);
+    const size_t img_bytes = image_bytes(w, h), nt = quality_tiles(c, n_images, w, h), g0 = (size_t)(n_images < c->n_slots ? n_images : c->n_slots);
+    unsigned long long *sse_part = nullptr, *sse = nullptr;
+    double *ssim_part = nullptr, *ssim = nullptr;
+    uint8_t* a_stage = nullptr;
+    rc = carve_analysis(c, [&](Carve& k) {
+        sse_part = k.take<unsigned long long>(nt); ssim_part = k.take<double>(nt);
+        sse = k.take<unsigned long long>(g0 * 3); ssim = k.take<double>(g0 * 3); a_stage = k.take<uint8_t>(g0 * img_bytes);
+    });
     if (rc) return rc;
-    unsigned long long* sse = (unsigned long long*)((char*)c->an_buf + part);
-    double* ssim = (double*)(sse + (size_t)g0 * 3);
-    uint8_t* a_stage = (uint8_t*)c->an_buf + stage_off;
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
-        HIPCHK(c, hipMemcpyAsync(a_stage, a + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->out_pool, b + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, c->stream));
-        rc = quality_chunk(c, g, a_stage, c->out_pool, P, sse, ssim_out ? ssim : nullptr);
+    const std::vector<HostArray> in = {{a, a_stage, img_bytes}, {b, c->out_pool, img_bytes}};
+    const std::vector<HostArray> out = {{sse_out, sse, 3 * sizeof(uint64_t)}, {ssim_out, ssim, 3 * sizeof(double)}};
+    return for_images(n_images, c->n_slots, [&](int i0, int g) -> int {
+        rc = upload(c, in, i0, g, c->stream);
         if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(sse_out + (size_t)i0 * 3, sse, (size_t)g * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        if (ssim_out) HIPCHK(c, hipMemcpyAsync(ssim_out + (size_t)i0 * 3, ssim, (size_t)g * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return TFFT_OK;
+        HIPCHK(c, launch_quality(a_stage, c->out_pool, P, g, sse_part, ssim_part, sse, ssim_out ? ssim : nullptr, c->stream));
+        return download_sync(c, out, i0, g, c->stream);
+    });
 }
 
 // ---- robustness analysis: channels over a stego batch, and the errors of what the extractor then reads
@@ -2678,24 +2691,17 @@ int channel_chunk(tfft_ctx* c, const tfft_channel& ch, const uint8_t* in, uint8_
     }
 }
 
-// the robustness scratch: [results of a chunk, n_channels x n_slots x 4 words (host form)] [status] [header] [payload] [attacked images]
+// the scratch of the robustness calls: [results of a chunk, n_channels x n_slots x 4 words (host form)] [status] [header] [payload] [attacked images]
 struct RobustBufs { uint32_t* res; int* status; uint8_t* hdr; uint8_t* pay; uint8_t* img; };
-int ensure_robust(tfft_ctx* c, int n_channels, uint64_t plen, size_t img_bytes, RobustBufs* b) {
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+int robust_bufs(tfft_ctx* c, int n_channels, uint64_t plen, size_t img_bytes, RobustBufs* b) {
     const size_t n = (size_t)c->n_slots;
-    const size_t o_status = up((size_t)n_channels * n * 16), o_hdr = o_status + up(n * sizeof(int)), o_pay = o_hdr + up(n * kHeaderBytes);
-    const size_t o_img = o_pay + up(n * plen), bytes = o_img + n * img_bytes;
-    if (!c->rb_buf || bytes > c->rb_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));      // an earlier call may still read it (like ensure_analysis: never part of a cached sequence)
-        (void)hipFree(c->rb_buf); c->rb_buf = nullptr; c->rb_cap = 0;
-        const size_t cap = grown(bytes, 4096);
-        int rc = dev_alloc(c, &c->rb_buf, cap);
-        if (rc) return rc;
-        c->rb_cap = cap;
-    }
-    char* p = (char*)c->rb_buf;
-    *b = RobustBufs{(uint32_t*)p, (int*)(p + o_status), (uint8_t*)(p + o_hdr), (uint8_t*)(p + o_pay), (uint8_t*)(p + o_img)};
-    return TFFT_OK;
+    return carve_analysis(c, [&](Carve& k) {
+        b->res = k.take<uint32_t>((size_t)n_channels * n * 4);
+        b->status = k.take<int>(n);
+        b->hdr = k.take<uint8_t>(n * kHeaderBytes);
+        b->pay = k.take<uint8_t>(n * plen);
+        b->img = k.take<uint8_t>(n * img_bytes);
+    });
 }
 int robust_args(const tfft_ctx* c, int n_images, const void* stego, int w, int h, const void* bins, uint64_t n_bins, double alpha, const void* header,
                 const void* payload, uint64_t plen, const tfft_channel* ch, int n_channels, const void* result) {
@@ -2734,13 +2740,10 @@ int tfft_channel_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w
     int rc = channel_args(c, n_images, rgb_dev, w, h, ch, 1, rgb_out_dev);
     if (rc) return rc;
     const size_t img_bytes = image_bytes(w, h);
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
-        rc = channel_chunk(c, *ch, (const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, (uint8_t*)rgb_out_dev + (size_t)i0 * img_bytes, g, w, h,
-                           first_image + (uint64_t)i0, c->stream);
-        if (rc) return rc;
-    }
-    return TFFT_OK;
+    return for_images(n_images, c->n_slots, [&](int i0, int g) {
+        return channel_chunk(c, *ch, nth((const uint8_t*)rgb_dev, i0, img_bytes), nth((uint8_t*)rgb_out_dev, i0, img_bytes), g, w, h,
+                             first_image + (uint64_t)i0, c->stream);
+    });
 }
 
 // host buffers: a chunk of n_slots images at a time, attacked in place in the analysis scratch (the slots' image buffers stay as they are)
@@ -2748,18 +2751,15 @@ int tfft_channel_batch(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int
     int rc = channel_args(c, n_images, rgb, w, h, ch, 1, rgb_out);
     if (rc) return rc;
     const size_t img_bytes = image_bytes(w, h);
-    rc = ensure_analysis(c, (size_t)(n_images < c->n_slots ? n_images : c->n_slots) * img_bytes);
+    uint8_t* stage = nullptr;
+    rc = carve_analysis(c, [&](Carve& k) { stage = k.take<uint8_t>((size_t)(n_images < c->n_slots ? n_images : c->n_slots) * img_bytes); });
     if (rc) return rc;
-    uint8_t* stage = (uint8_t*)c->an_buf;
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
-        HIPCHK(c, hipMemcpyAsync(stage, rgb + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, c->stream));
-        rc = channel_chunk(c, *ch, stage, stage, g, w, h, first_image + (uint64_t)i0, c->stream);
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(rgb_out + (size_t)i0 * img_bytes, stage, (size_t)g * img_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return TFFT_OK;
+    return for_images(n_images, c->n_slots, [&](int i0, int g) {
+        rc = upload(c, {{rgb, stage, img_bytes}}, i0, g, c->stream);
+        if (!rc) rc = channel_chunk(c, *ch, stage, stage, g, w, h, first_image + (uint64_t)i0, c->stream);
+        if (!rc) rc = download_sync(c, {{rgb_out, stage, img_bytes}}, i0, g, c->stream);
+        return rc;
+    });
 }
 
 int tfft_robustness_batch_dev(tfft_ctx* c, int n_images, const void* stego_dev, int w, int h, int center, const void* bins_dev, uint64_t n_bins,
@@ -2771,7 +2771,7 @@ int tfft_robustness_batch_dev(tfft_ctx* c, int n_images, const void* stego_dev, 
     const size_t img_bytes = image_bytes(w, h);
     RobustBufs b;
     rc = ensure_stream(c, n_bins);
-    if (!rc) rc = ensure_robust(c, 0, payload_len, img_bytes, &b);
+    if (!rc) rc = robust_bufs(c, 0, payload_len, img_bytes, &b);
     if (rc) return rc;
     const ChunkArgs a = ChunkArgs::list(bins_dev, n_bins, alpha);
     return for_chunks(c, n_images, w, h, center, false, nullptr, [&](const Chunk& k) {
@@ -2782,7 +2782,7 @@ int tfft_robustness_batch_dev(tfft_ctx* c, int n_images, const void* stego_dev, 
 }
 
 // host buffers: a chunk of n_slots stegos at a time in the slots' image buffers, the list, the frames and the chunk's counts in the staging
-// buffers of the host pipelines and the robustness scratch
+// buffers of the host pipelines and the analysis scratch
 int tfft_robustness_batch(tfft_ctx* c, int n_images, const uint8_t* stego, int w, int h, int center, const tfft_bin* bins, uint64_t n_bins, double alpha,
                           const uint8_t* header, const uint8_t* payload, uint64_t payload_len, const tfft_channel* channels, int n_channels,
                           uint64_t first_image, uint32_t* result_out) {
@@ -2794,24 +2794,20 @@ int tfft_robustness_batch(tfft_ctx* c, int n_images, const uint8_t* stego, int w
     rc = ensure_stream(c, n_bins);
     if (!rc) rc = ensure_stream_io(c, payload_len);
     if (!rc) rc = ensure_stage(c, n_bins);
-    if (!rc) rc = ensure_robust(c, n_channels, payload_len, img_bytes, &b);
+    if (!rc) rc = robust_bufs(c, n_channels, payload_len, img_bytes, &b);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->stage_bins, bins, n_bins * sizeof(tfft_bin), hipMemcpyHostToDevice, c->stream));
     const ChunkArgs a = ChunkArgs::list(c->stage_bins, n_bins, alpha);
-    rc = for_chunks(c, n_images, w, h, center, false, nullptr, [&](const Chunk& k) -> int {
-        hipStream_t st = k.st;
-        for (int i = 0; i < k.g; i++) { c->slots[i].has_spec = false; c->slots[i].rgb_src = nullptr; }      // their images go now
-        HIPCHK(c, hipMemcpyAsync(c->img(0), stego + (size_t)k.i1 * img_bytes, (size_t)k.g * img_bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->sio_hdr, header + (size_t)k.i1 * kHeaderBytes, (size_t)k.g * kHeaderBytes, hipMemcpyHostToDevice, st));
-        if (payload_len) HIPCHK(c, hipMemcpyAsync(c->sio_pay, payload + (size_t)k.i1 * payload_len, (size_t)k.g * payload_len, hipMemcpyHostToDevice, st));
-        const int rc1 = robust_chunk(c, k, a, c->img(0), c->sio_hdr, c->sio_pay, payload_len, w, h, channels, n_channels, first_image + (uint64_t)k.i1, b,
+    const std::vector<HostArray> in = {{stego, c->img(0), img_bytes}, {header, c->sio_hdr, kHeaderBytes}, {payload, c->sio_pay, payload_len}};
+    std::vector<HostArray> out;      // channel q's counts: n_images x 4 words of the result, n_slots x 4 words of the scratch
+    for (int q = 0; q < n_channels; q++) out.push_back({result_out + (size_t)q * n_images * 4, b.res + (size_t)q * c->n_slots * 4, 4 * sizeof(uint32_t)});
+    rc = for_chunks(c, n_images, w, h, center, false, nullptr, [&](const Chunk& k) {
+        drop_images(c, k.g);      // their images go now
+        int rc1 = upload(c, in, k.i1, k.g, k.st);
+        if (!rc1) rc1 = robust_chunk(c, k, a, c->img(0), c->sio_hdr, c->sio_pay, payload_len, w, h, channels, n_channels, first_image + (uint64_t)k.i1, b,
                                      b.res, (size_t)c->n_slots);
-        if (rc1) return rc1;
-        for (int q = 0; q < n_channels; q++)
-            HIPCHK(c, hipMemcpyAsync(result_out + ((size_t)q * n_images + k.i1) * 4, b.res + (size_t)q * c->n_slots * 4, (size_t)k.g * 4 * sizeof(uint32_t),
-                                     hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        return TFFT_OK;
+        if (!rc1) rc1 = download_sync(c, out, k.i1, k.g, k.st);
+        return rc1;
     });
     if (rc) return rc;
     return check_err_flag(c);
@@ -2834,11 +2830,10 @@ int tfft_spam_batch_dev(tfft_ctx* c, int n_images, const void* rgb_dev, int w, i
     int rc = spam_args(c, n_images, rgb_dev, w, h, t, counts_out_dev);
     if (rc) return rc;
     const size_t img_bytes = image_bytes(w, h), words = spam_words(t);
-    for (int i0 = 0; i0 < n_images; i0 += 65535) {
-        const int g = n_images - i0 < 65535 ? n_images - i0 : 65535;
-        HIPCHK(c, launch_spam((const uint8_t*)rgb_dev + (size_t)i0 * img_bytes, w, h, g, t, (uint32_t*)counts_out_dev + (size_t)i0 * words, c->stream));
-    }
-    return TFFT_OK;
+    return for_images(n_images, 65535, [&](int i0, int g) -> int {
+        HIPCHK(c, launch_spam(nth((const uint8_t*)rgb_dev, i0, img_bytes), w, h, g, t, nth((uint32_t*)counts_out_dev, i0, words), c->stream));
+        return TFFT_OK;
+    });
 }
 
 // host buffers: a chunk of n_slots images at a time, staged in the analysis scratch behind the chunk's counts (the slots' image buffers
@@ -2847,20 +2842,17 @@ int tfft_spam_batch(tfft_ctx* c, int n_images, const uint8_t* rgb, int w, int h,
     int rc = spam_args(c, n_images, rgb, w, h, t, counts_out);
     if (rc) return rc;
     const size_t img_bytes = image_bytes(w, h), words = spam_words(t);
-    const int g0 = n_images < c->n_slots ? n_images : c->n_slots;
-    const size_t stage_off = ((size_t)g0 * words * sizeof(uint32_t) + 255) / 256 * 256;
-    rc = ensure_analysis(c, stage_off + (size_t)g0 * img_bytes);
+    const size_t g0 = (size_t)(n_images < c->n_slots ? n_images : c->n_slots);
+    uint32_t* cnt = nullptr;
+    uint8_t* stage = nullptr;
+    rc = carve_analysis(c, [&](Carve& k) { cnt = k.take<uint32_t>(g0 * words); stage = k.take<uint8_t>(g0 * img_bytes); });
     if (rc) return rc;
-    uint32_t* cnt = (uint32_t*)c->an_buf;
-    uint8_t* stage = (uint8_t*)c->an_buf + stage_off;
-    for (int i0 = 0; i0 < n_images; i0 += c->n_slots) {
-        const int g = (n_images - i0 < c->n_slots) ? n_images - i0 : c->n_slots;
-        HIPCHK(c, hipMemcpyAsync(stage, rgb + (size_t)i0 * img_bytes, (size_t)g * img_bytes, hipMemcpyHostToDevice, c->stream));
+    return for_images(n_images, c->n_slots, [&](int i0, int g) -> int {
+        rc = upload(c, {{rgb, stage, img_bytes}}, i0, g, c->stream);
+        if (rc) return rc;
         HIPCHK(c, launch_spam(stage, w, h, g, t, cnt, c->stream));
-        HIPCHK(c, hipMemcpyAsync(counts_out + (size_t)i0 * words, cnt, (size_t)g * words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return TFFT_OK;
+        return download_sync(c, {{counts_out, cnt, words * sizeof(uint32_t)}}, i0, g, c->stream);
+    });
 }
 
 void* tfft_host_alloc(size_t bytes) {
