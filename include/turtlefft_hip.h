@@ -103,6 +103,13 @@ int tfft_exact_info(const tfft_ctx* ctx, int n_fp64[3]);
 /* Diagnostic: how the last tfft_medians / batched median of `slot` was obtained, per plane:
  * 1 = sampled bracket + one verified pass (fast path), 0 = full three-level select (fallback). */
 int tfft_median_path(tfft_ctx* ctx, int slot, int fast[3]);
+/* Diagnostics of the batched embeds.  tfft_batch_medians: the fp32 medians |F| the statistics of the last batched embed left for the image
+ * in `slot` (image i of a call's last chunk sits in slot i; no fp64 settling, nothing recomputed).  Synchronises.
+ * tfft_embed_plan_info: the launch sequence the last chunk of the last batched embed took -- info[0] = 1: delta embedding; info[1]: the
+ * statistics (0 none, 1 inside the last forward column step, 2 medians + capacity in one sequence, 3 separate passes); info[2] = 1: that
+ * step also embedded and ran the first inverse column step (one launch for the pair); info[3] = 1: statistics on the side stream. */
+int tfft_batch_medians(tfft_ctx* ctx, int slot, float med[3]);
+int tfft_embed_plan_info(const tfft_ctx* ctx, int info[4]);
 
 /* count_plane (S:998-1008): sum over planes of floor(c/2), c = bins in the
  * annulus [rmin,rmax]*min(PH,PW), off the axes, |F| >= thr[plane].  Synchronises.

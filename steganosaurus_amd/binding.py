@@ -38,6 +38,8 @@ SYMBOLS = {
     "tfft_forward_rgb8_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _pi, _pi]),
     "tfft_medians": (_i, [_vp, _i, _vp]),
     "tfft_median_path": (_i, [_vp, _i, _vp]),
+    "tfft_batch_medians": (_i, [_vp, _i, _vp]),
+    "tfft_embed_plan_info": (_i, [_vp, _pi]),
     "tfft_capacity": (_i, [_vp, _i, _d, _d, _vp, C.POINTER(_u64)]),
     "tfft_lowfreq_mag": (_i, [_vp, _i, _i, _vp]),
     "tfft_embed_bins": (_i, [_vp, _i, _vp, _vp, _vp, _u64, _d, _i, _vp]),
@@ -340,6 +342,19 @@ class Context:
         out = np.zeros(3, np.int32)
         _check(self.lib.tfft_median_path(self.h, slot, _ptr(out)), "tfft_median_path")
         return out
+
+    def batch_medians(self, n):
+        """fp32 medians the last batched embed's statistics left for the images in slots 0 .. n-1: (n, 3)"""
+        out = np.zeros((n, 3), np.float32)
+        for i in range(n):
+            _check(self.lib.tfft_batch_medians(self.h, i, _ptr(out[i])), "tfft_batch_medians")
+        return out
+
+    def embed_plan_info(self):
+        """the launch sequence the last chunk of the last batched embed took"""
+        info = (C.c_int * 4)()
+        _check(self.lib.tfft_embed_plan_info(self.h, info), "tfft_embed_plan_info")
+        return {"delta": bool(info[0]), "stats": int(info[1]), "tile_fuse": bool(info[2]), "side": bool(info[3])}
 
     def capacity(self, thr, rmin=0.05, rmax=0.45, slot=0):
         thr = np.ascontiguousarray(thr, np.float64)

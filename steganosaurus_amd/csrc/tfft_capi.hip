@@ -59,6 +59,9 @@ struct tfft_ctx {
     int stats_prio = 1;                   // the statistics' side stream at the lowest stream priority
     int stats_tile = 1;                   // batched delta embeds run the statistics' bracket pass inside the last forward column step and never store
                                           // the spectrum or |F|^2 (TFFT_STATS_TILE=0: |F|^2 planes + the statistics kernels over them, round 2's default)
+    int embed_tile_fuse = 1;              // batched delta embeds with in-step statistics: that step also embeds and runs the first inverse step on the tile it
+                                          // holds (COLS_STAT_EMBED).  TFFT_EMBED_TILE_FUSE=0: two launches; 1: launches of >= 2^24 bins; 2: wherever COLS_STAT runs
+    int last_embed_path[4] = {0, 0, 0, 0};      // tfft_embed_plan_info: the EmbedPath of the last embed chunk (delta, stats, tile_fuse, side)
     int stats_tile_step_forced = 0;
     int stats_tile_step = 8;              // every 8th column tile is the sample (TFFT_STATS_TILE_STEP)
     float2* col0_pool = nullptr;          // [n_slots*3*max_ph] the packed column 0 of batched embeds that store |F|^2 planes (ColParams::st_col0)
@@ -274,6 +277,7 @@ struct StageMode {
                                            // in the step its launch sequence runs in a bucket mode, and the flag goes with that step (a COLS_PLAIN
                                            // or COLS_ROWLIMIT step has no lists: launch_cols rejects it with the flag set)
     const uint8_t* inv_cover = nullptr;    // the inverse row kernel adds its transform to these cover pixels (delta embedding)
+    bool inv_first_done = false;           // the first inverse column step ran inside the last forward one (COLS_STAT_EMBED, which left its output in `spec`)
     bool inv_via_spec = false;             // delta embedding: the inverse keeps its intermediate in `spec` (nothing reads F there), so `tmp` -- the
                                            // input of the last forward step -- survives for the gated fallback of the in-kernel statistics
 };
@@ -303,11 +307,13 @@ static int last_forward_params(tfft_ctx* c, const Slot& s, const ColPlan& pl, co
             if (cp.tile_step > 1) cp.tiles_per_block = cp.hist_sel ? 2 : 1;      // the sample: an eighth of the tiles; few per workgroup keep the grid wide
             break;
         case COLS_READ: cp.trash = c->trash; cp.tiles_per_block = c->cols_tiles_read; break;
-        case COLS_EMIT: case COLS_STAT:
+        case COLS_EMIT: case COLS_STAT: case COLS_STAT_EMBED:
             cp.trash = c->trash;
-            cp.em_jp = nullptr; cp.em_med = nullptr; cp.em_alpha = 0.f;      // (the phase options belong to COLS_EMBED, whose object this may be)
+            // (the phase options belong to COLS_EMBED, whose object this may be -- and to the step that embeds in the same visit)
+            if (md.fwd_mode != COLS_STAT_EMBED) cp.em_jp = nullptr;
+            cp.em_med = nullptr; cp.em_alpha = 0.f;
             if (!c->cols_tiles_forced && pl.log_n2 <= 8) cp.tiles_per_block = 2;
-            if (md.fwd_mode == COLS_STAT && c->cols_tiles_stat) cp.tiles_per_block = c->cols_tiles_stat;
+            if (stat_mode(md.fwd_mode) && c->cols_tiles_stat) cp.tiles_per_block = c->cols_tiles_stat;
             break;
     }
     return dc_tables(c, s, cp);
@@ -395,6 +401,7 @@ int enqueue_forward(tfft_ctx* c, int s0, int n, const uint8_t* rgb_dev, hipStrea
 // inverse: columns (spec -> tmp, only rows < H kept) then rows (tmp -> u8)
 int enqueue_inverse(tfft_ctx* c, int s0, int n, uint8_t* rgb_out_dev, hipStream_t st, const StageMode& md = StageMode()) {
     for (int stage : {COLS_INV_A, COLS_INV_B, ROWS_INV}) {
+        if (stage == COLS_INV_A && md.inv_first_done) continue;
         int rc = enqueue_fft_stage(c, s0, n, stage, nullptr, rgb_out_dev, st, md);
         if (rc) return rc;
     }
@@ -649,6 +656,7 @@ int tfft_create(int device, int max_w, int max_h, int n_slots, tfft_ctx** out) {
     if (const char* e = getenv("TFFT_EXACT_STATS")) c->exact_stats = atoi(e);
     if (const char* e = getenv("TFFT_BATCH_EXACT_TRACE")) c->bx_trace = atoi(e);
     if (const char* e = getenv("TFFT_STATS_TILE")) c->stats_tile = atoi(e);
+    if (const char* e = getenv("TFFT_EMBED_TILE_FUSE")) c->embed_tile_fuse = atoi(e);
     if (const char* e = getenv("TFFT_STATS_PRIO")) c->stats_prio = atoi(e);
     if (const char* e = getenv("TFFT_STATS_FAIL_ONCE")) c->stats_fail_once = atoi(e);
     if (const char* e = getenv("TFFT_STATS_TILE_STEP")) { c->stats_tile_step = atoi(e); if (c->stats_tile_step < 8) c->stats_tile_step = 8; c->stats_tile_step_forced = 1; }
@@ -928,6 +936,7 @@ struct ChunkArgs {
     // one walk per image (tfft_*_stream_batch_walks*, the fitted embed): `bins` are a chunk's g lists, image i's at bins + i*n_bits; jitter
     // (the same layout, or nullptr) and adaptive alpha come with them instead of from the context's phase options
     bool per_image = false; const float* jit = nullptr; bool adaptive = false;
+    bool values_wanted = false;      // the caller reads the listed bins' values (the `fl` list) after the embed: the fitted embed
     static ChunkArgs list(const void* bins, uint64_t n_bits, double alpha) {
         ChunkArgs a;
         a.bins = (const tfft_bin*)bins; a.n_bits = n_bits; a.alpha = alpha;
@@ -940,6 +949,7 @@ struct ChunkArgs {
         return *this;
     }
     ChunkArgs& walks(const void* j, int adapt) { per_image = true; jit = (const float*)j; adaptive = adapt != 0; return *this; }
+    ChunkArgs& values() { values_wanted = true; return *this; }
     bool framed() const { return hdr != nullptr; }
     uint64_t stream_len() const { return limit < n_bits ? limit : n_bits; }      // the bits an image carries
     ChunkArgs from(size_t i) const {
@@ -1202,6 +1212,18 @@ int tfft_median_path(tfft_ctx* c, int slot, int fast[3]) {
     for (int i = 0; i < 3; i++) fast[i] = (h[i].done == 1 && h[i].fast) ? 1 : 0;
     free(h);
     if (e != hipSuccess) { c->last_hip = (int)e; return TFFT_E_HIP; }
+    return TFFT_OK;
+}
+
+int tfft_batch_medians(tfft_ctx* c, int slot, float med[3]) {
+    if (!slot_ok(c, slot) || !med) return TFFT_E_INVALID;
+    HIPCHK(c, hipMemcpyAsync(med, c->med + 3 * slot, 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TFFT_OK;
+}
+int tfft_embed_plan_info(const tfft_ctx* c, int info[4]) {
+    if (!c || !info) return TFFT_E_INVALID;
+    for (int i = 0; i < 4; i++) info[i] = c->last_embed_path[i];
     return TFFT_OK;
 }
 
@@ -1564,6 +1586,16 @@ static bool tilestats_applies(const tfft_ctx* c, const Slot& s, const ColPlan& p
            (unsigned long long)s.PH * s.PWi <= TFFT_COMPACT_MAX_BINS && (s.PWi / 2) % 16 == 0;
 }
 
+// ... and does that step embed and run the first inverse column step on the same tile (COLS_STAT_EMBED)?  By default where the in-step
+// statistics apply by their own size rule (a small launch forced into COLS_STAT by TFFT_STATS_TILE=2 keeps the pair); not with exact
+// capacities on (their settle pass is kept on the sequence it was validated with).  L = 512 gains as L = 256 does (8 x 4K embed 2.47 ->
+// 2.38 ms).  Not at L = 16, whatever the knob: with the DC term the fused form needs 220 registers where COLS_STAT needs
+// 168 -- two workgroups per CU instead of three -- and nobody measured it; launch_cols has no such instantiation
+static bool tile_fuse_applies(const tfft_ctx* c, const Slot& s, const ColPlan& pl, int n) {
+    if (c->embed_tile_fuse <= 0 || c->bx_mode || pl.log_n2 < TFFT_TILE_FUSE_MIN_LOG) return false;
+    return c->embed_tile_fuse >= 2 || (unsigned long long)n * s.PH * s.PWi >= (1ull << 24);
+}
+
 // The statistics after COLS_STAT, in two parts so that the first can run beside the inverse transform (embed_chunk):
 //   select: the medians out of the staged candidates (5 small dependent launches, ~75 us of latency for a 32 x 1080p launch)
 //   tail  : images with a plane the fast path could not settle get their spectrum after all -- the plain last forward step, gated (it
@@ -1589,9 +1621,9 @@ static int enqueue_tilestats_tail(tfft_ctx* c, int s0, int g, const uint8_t* rgb
 
 // forward transform + statistics of slots [s0, s0+g) without a stored spectrum (see ColParams::st_*): em carries the delta-embedding lists
 // phases (tfft_profile_stage times them apart): 1 the steps before the last column step, 2 sample + bracket guess, 4 the COLS_STAT step,
-// 8 select, 16 gated spectrum + fallbacks + capacity
+// 8 select, 16 gated spectrum + fallbacks + capacity.  tile_fuse: the COLS_STAT step embeds and runs the first inverse step too (EmbedPath::tile_fuse)
 static int enqueue_forward_tilestats(tfft_ctx* c, int s0, int g, const uint8_t* rgb_in, hipStream_t st, const ColParams& em, bool walks,
-                                     const CapParams& cap, unsigned long long* usable, int phases = 31) {
+                                     const CapParams& cap, unsigned long long* usable, bool tile_fuse, int phases = 31) {
     const Slot& s = c->slots[s0];
     const ColPlan pl = plan_cols(c, s.PH, s.PWi, g);
     const int final_fwd = pl.direct ? COLS_FWD_A : COLS_FWD_B;
@@ -1635,7 +1667,7 @@ static int enqueue_forward_tilestats(tfft_ctx* c, int s0, int g, const uint8_t* 
         sp.st_sel = sb.st; sp.st_cand = sb.cand; sp.st_cand_stride = sb.cand_stride; sp.st_partial = sb.partial; sp.st_amb = sb.amb; sp.st_col0 = sb.col0;
         sp.st_slo = cap.s_lo > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)cap.s_lo; sp.st_shi = cap.s_hi > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)cap.s_hi;
         sp.st_cap = 1; sp.st_PW = cap.PW;
-        StageMode me; me.fwd_mode = COLS_STAT; me.fwd = &sp; me.walks = walks;
+        StageMode me; me.fwd_mode = tile_fuse ? COLS_STAT_EMBED : COLS_STAT; me.fwd = &sp; me.walks = walks;
         rc = enqueue_fft_stage(c, s0, g, final_fwd, rgb_in, nullptr, st, me);
         if (rc) return rc;
     }
@@ -1683,11 +1715,12 @@ enum StatsForm { STATS_NONE, STATS_IN_STEP, STATS_FUSED, STATS_SEPARATE };
 enum FwdStore { STORE_SPEC = 0, STORE_M2 = 1, STORE_NONE = 2 };
 // delta: stego = cover + IFFT(F' - F) from the bucketed lists (else F' is written into the spectrum, k_embed, and inverted); side: the
 // statistics run on the side stream, beside the inverse transform
-struct EmbedPath { bool delta; StatsForm stats; FwdStore store; bool side; };
+// tile_fuse: the in-step statistics' launch is COLS_STAT_EMBED -- no COLS_EMBED launch, no values through the fl list
+struct EmbedPath { bool delta; StatsForm stats; FwdStore store; bool side; bool tile_fuse; };
 // stats: the chunk runs the statistics (capacities asked for, or adaptive alpha: see embed_chunk)
 static EmbedPath embed_path(const tfft_ctx* c, const Slot& s, int g, const ChunkArgs& a, bool stats) {
     // (delta whatever the chunk size: the bytes of a stego image do not depend on how the batch was cut)
-    EmbedPath p{c->embed_delta && a.alpha > 0.0 && a.alpha < M_PI && a.n_bits > 0, STATS_NONE, STORE_SPEC, false};
+    EmbedPath p{c->embed_delta && a.alpha > 0.0 && a.alpha < M_PI && a.n_bits > 0, STATS_NONE, STORE_SPEC, false, false};
     if (!stats && p.delta && c->stats_m2) p.store = STORE_NONE;      // nobody reads the spectrum of a delta embed
     if (!stats) return p;
     const CapParams cap = cap_params(c, s, a.rmin, a.rmax);
@@ -1696,6 +1729,7 @@ static EmbedPath embed_path(const tfft_ctx* c, const Slot& s, int g, const Chunk
     if (tilestats_applies(c, s, plan_cols(c, s.PH, s.PWi, g), cap, g)) p.stats = STATS_IN_STEP;
     else if (stats_m2_applies(c, s, cap)) p.store = STORE_M2;
     p.side = c->stats_async && !phase_opts(c, a).adaptive;      // (adaptive: the embed waits for the medians)
+    p.tile_fuse = tile_fuse_applies(c, s, plan_cols(c, s.PH, s.PWi, g), g) && p.stats == STATS_IN_STEP && !phase_opts(c, a).adaptive && !a.values_wanted;
     return p;
 }
 // The spectrum is only ever read at the bins of the list.  READ_TILES: the bins bucketed by column tile, the last forward column step reads
@@ -1728,6 +1762,7 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, hipStream_t st, const Ch
     if (ph.rc) return ph.rc;
     const EmbedPath path = embed_path(c, s, g, a, usable != nullptr);
     const bool in_step = path.stats == STATS_IN_STEP;
+    c->last_embed_path[0] = path.delta; c->last_embed_path[1] = (int)path.stats; c->last_embed_path[2] = path.tile_fuse; c->last_embed_path[3] = path.side;
     EmbedParams ep = embed_params(c, s, n_bits, a.alpha, ph.adaptive, nullptr, ph.jit != nullptr);
     if (walks) ep.bins_stride = n_bits;
     if (ph.adaptive) ep.med_dev = c->med + 3 * s0;      // (the statistics below run before the embed: see EmbedPath::side)
@@ -1763,7 +1798,7 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, hipStream_t st, const Ch
     // a plane's bracket turns out wrong: then the gated plain step of the tail produces the spectrum for the fallback kernels)
     StageMode md;
     if (path.delta) { md.fwd_mode = COLS_EMIT; md.fwd = &em; md.walks = walks; }
-    rc = in_step ? enqueue_forward_tilestats(c, s0, g, rgb_in, st, em, walks, cap, usable, 7) : enqueue_forward(c, s0, g, rgb_in, st, md);
+    rc = in_step ? enqueue_forward_tilestats(c, s0, g, rgb_in, st, em, walks, cap, usable, path.tile_fuse, 7) : enqueue_forward(c, s0, g, rgb_in, st, md);
     if (rc) return rc;
     // the statistics.  With delta embedding nothing downstream reads them unless alpha is adaptive: on a side stream beside the inverse
     // transform, which does not wait for them (the in-kernel form's select chain is five small dependent launches)
@@ -1792,6 +1827,7 @@ static int embed_chunk_impl(tfft_ctx* c, int s0, int g, hipStream_t st, const Ch
     }
     StageMode mi;
     mi.inv_mode = COLS_EMBED; mi.inv = &em; mi.walks = walks; mi.inv_cover = rgb_in; mi.inv_via_spec = in_step;
+    mi.inv_first_done = path.tile_fuse;
     rc = enqueue_inverse(c, s0, g, rgb_out, st, mi);
     if (path.side) {            // (also after a failed inverse.)  Whoever waits for the context's stream has the capacities too
         const int rj = stats_join(c, which, st);
@@ -2355,8 +2391,10 @@ static int fit_forward(tfft_ctx* c, int g, const uint8_t* rgb, hipStream_t st) {
 
 // One chunk of g <= n_slots images in slots [0, g), on the context's stream.  cover: the chunk's covers in buffers nothing writes during
 // the call; iters: host, g entries; wrong_dev: device, g entries
-static int fit_chunk(tfft_ctx* c, int g, const ChunkArgs& a, const uint8_t* cover, unsigned long long* usable, int max_iters, double margin,
+static int fit_chunk(tfft_ctx* c, int g, const ChunkArgs& a0, const uint8_t* cover, unsigned long long* usable, int max_iters, double margin,
                      uint8_t* rgb_out, int32_t* iters, uint32_t* wrong_dev) {
+    ChunkArgs a = a0;
+    a.values();      // F0 of the listed bins is read below: the forward step writes the list (EmbedPath::tile_fuse would not)
     hipStream_t st = c->stream;
     const Slot& s = c->slots[0];
     const tfft_bin* bins = a.bins;
@@ -2902,6 +2940,7 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
     // the statistics inside the last forward column step: that step is timed as COLS_STAT; MEDIANS is everything else of the
     // statistics -- sample pass + bracket guess before it, select chain, gated step, fallback and capacity kernels after it
     const bool tile = path.stats == STATS_IN_STEP && (stage == final_fwd || stage == MEDIANS);
+    if (stage == COLS_INV_A && path.tile_fuse) launches = 0;      // inside the last forward step's launch
     if (stage == CAPACITY) launches = path.stats == STATS_SEPARATE ? 2 : 0;      // else counted inside the medians' full pass
     if (stage == MEDIANS) {
         // tile: the sample pass and the gated plain step (FFT stages) + the statistics' own kernels around the COLS_STAT step
@@ -2959,7 +2998,10 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
         // phases of enqueue_forward_tilestats: 2 sample + guess, 4 COLS_STAT, 8 select, 16 tail.  The COLS_STAT step alone needs a bracket
         // (one untimed sample pass); MEDIANS = the whole sequence minus the COLS_STAT launches it contains, timed the same way
         float ms_all = 0.f, ms_stat = 0.f;
-        auto run = [&](int phases) { return enqueue_forward_tilestats(c, 0, n_images, (const uint8_t*)rgb_dev, c->stream, em, false, tcap, c->usable, phases); };
+        // (a fused launch scatters by the stream bits: gathered here, untimed, as the embed stage of the sequence would have before the
+        // parent's cols_inv_a -- in bench.py's order that stage comes after this one)
+        if (path.tile_fuse) HIPCHK(c, launch_gather_bits(c->tb[0].ent, c->tb[0].off + bg.nb, (const uint8_t*)bits_dev, nullptr, nullptr, 0, n_bits, n_bits, n_images, c->tb[0].pb, c->stream));
+        auto run = [&](int phases) { return enqueue_forward_tilestats(c, 0, n_images, (const uint8_t*)rgb_dev, c->stream, em, false, tcap, c->usable, path.tile_fuse, phases); };
         int rc = run(2);
         if (!rc) rc = timed([&] { return run(4); }, &ms_stat);
         if (!rc && stage == MEDIANS) rc = timed([&] { return run(2 | 4 | 8 | 16); }, &ms_all);
@@ -2979,8 +3021,10 @@ int tfft_profile_stage(tfft_ctx* c, int n_images, int stage, int reps, const voi
             case COLS_INV_A:
                 if (delta_lists) { md.inv_mode = COLS_EMBED; md.inv = &em; }
                 return fft_stage(stage, md);
+            case COLS_INV_B:
             case ROWS_INV:
                 if (path.delta && rgb_dev) md.inv_cover = (const uint8_t*)rgb_dev;
+                if (path.tile_fuse) { md.inv_mode = COLS_EMBED; md.inv_via_spec = true; }      // the intermediate is where COLS_STAT_EMBED left it
                 return fft_stage(stage, md);
             case COLS_FWD_READ:
                 md.fwd_mode = tile_read ? COLS_READ : COLS_ROWLIMIT; md.fwd = &rd;

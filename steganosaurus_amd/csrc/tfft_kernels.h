@@ -27,8 +27,10 @@ struct TileBin { uint16_t k; uint8_t c; uint8_t conj; uint32_t bit; };
 
 // The modes of a column step (k_fft_cols; what each does: the comment above the kernel).  The caller of launch_cols names the mode; the
 // groups of ColParams below say which mode reads them
-enum { COLS_PLAIN = 0, COLS_ROWLIMIT = 1, COLS_READ = 2, COLS_EMBED = 3, COLS_EMIT = 4, COLS_STAT = 5, COLS_EMBED_D = 6 };
+enum { COLS_PLAIN = 0, COLS_ROWLIMIT = 1, COLS_READ = 2, COLS_EMBED = 3, COLS_EMIT = 4, COLS_STAT = 5, COLS_EMBED_D = 6, COLS_STAT_EMBED = 7 };
 constexpr bool embed_mode(int mode) { return mode == COLS_EMBED || mode == COLS_EMBED_D; }      // the first inverse step of a delta embed
+#define TFFT_TILE_FUSE_MIN_LOG 5      // COLS_STAT_EMBED exists from L = 32 on (at L = 16 it holds fewer workgroups per CU than COLS_STAT)
+constexpr bool stat_mode(int mode) { return mode == COLS_STAT || mode == COLS_STAT_EMBED; }      // the statistics' bracket pass inside the last forward step
 
 // one column step as launch_cols runs it
 struct ColStep {
@@ -67,6 +69,8 @@ struct ColParams {
     const float2* em_jp;             // jitter as unit phasors (cos j, sin j), indexed like rd_bins (shared by all images); nullptr = no jitter
     const float* em_med;             // COLS_EMBED, adaptive alpha: 3 medians |F| per image of the launch; nullptr = the fixed em_cos / em_sin
     float em_alpha;                  // ... and the alpha they scale (S:704-710)
+    // COLS_STAT_EMBED: COLS_STAT and COLS_EMBED in one visit per tile -- reads `in`, writes the first inverse step's output to `out`; the st_*
+    // fields of COLS_STAT, em_pb / em_cos / em_sin / em_jp of COLS_EMBED; em_fl only for bucket entries beyond those a thread keeps in registers
     // statistics inside the last forward step (COLS_STAT = COLS_EMIT without the spectrum store): every value is classified against
     // the bracket of its plane's SelectState exactly as k_collect_bracket does (weight below, candidates, capacity counts, parked
     // values); the packed column 0 goes to st_col0 for k_col0_stats

@@ -890,6 +890,11 @@ __device__ __forceinline__ int read_bit_value(float2 v, const EmbedParams& P, in
 //   COLS_EMBED_D   COLS_EMBED with F' - F not computed from (F, bit, alpha) but taken as it is from P.em_fl: one value per bucket entry,
 //                  in the coordinates of the stored bin -- the corrected deltas of the fitted embed (tfft_embed_stream_batch_fit_dev,
 //                  DESIGN.md section 10).  One walk per image only (PI)
+//   COLS_STAT_EMBED  COLS_STAT and COLS_EMBED of the same (row group, column tile) in one visit: the tile of `in` is transformed and
+//                  classified as in COLS_STAT; F at the tile's listed bins is read from the parked tile (not through P.em_fl), the tile is
+//                  zeroed, receives F' - F, is transformed back and stored to `out` with the inverse step's output twiddles.  The inverse
+//                  step's output rows are the forward step's input rows (k + L*g), so the stores go where the loads came from, in the
+//                  other buffer: `in` survives for the statistics' gated tail.  Two-step plans only (SIGN = +1 names the first half)
 __device__ __forceinline__ unsigned frame_bit(const uint8_t* __restrict__ header, const uint8_t* __restrict__ payload, uint64_t i);   // defined with k_embed
 // DC: the DC-removal epilogue (ColParams::dc_*) is compiled in; its own instantiation, because the kernel sits at the
 // 256-VGPR cap and even the unused code costs accumulation-register spills
@@ -908,7 +913,10 @@ template <int LOGL, int SIGN, int MODE = COLS_PLAIN, bool DC = false, bool TW = 
 __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE == COLS_EMIT && TFFT_COLS_PFEMIT) ? 1 : (FULL ? TFFT_COLS_WAVES(LOGL) : imin(2, TFFT_COLS_WAVES(LOGL)))) k_fft_cols(const float2* in, float2* out, const float2* __restrict__ tw,
                            ColParams P) {
     constexpr int L = 1 << LOGL, E = elems_for(L), T = L / E, C = 16;
-    const int c = threadIdx.x, t = threadIdx.y, gl = threadIdx.z;
+    constexpr bool STAT = stat_mode(MODE), FUSED = (MODE == COLS_STAT_EMBED);
+    // (COLS_STAT_EMBED from L = 256 on: one group per workgroup -- launch_cols_t -- and said so here, the group and what follows from it
+    // are scalars: left as threadIdx.z the kernel spilled 14 registers of such per-thread copies at four waves per SIMD)
+    const int c = threadIdx.x, t = threadIdx.y, gl = (FUSED && T * C >= 256) ? 0 : (int)threadIdx.z;
     const int g = (MODE == COLS_PLAIN && SIGN > 0 && FULL && P.g_step > 1) ? (int)(blockIdx.y * blockDim.z + gl) * P.g_step + P.g_off      // the statistics' sample
                                                                             : (int)(blockIdx.y * blockDim.z + gl);
     const int img = blockIdx.z / 3, plane = blockIdx.z - 3 * img;      // grid.z = 3 * n_images
@@ -992,7 +1000,16 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
     float2* lds_ah = reinterpret_cast<float2*>(tfft_smem) + (size_t)blockDim.z * L * C + (size_t)gl * L;
     // output twiddles of the two-step decomposition, exp(SIGN*2*pi*i*k*g/PH), k < L: staged once per workgroup behind the DC rows
     // and read back at the stores (as registers they were 32 VGPRs: the L = 256 / 512 variants spilled 26 .. 79 dwords)
-    float2* lds_wo = reinterpret_cast<float2*>(tfft_smem) + (size_t)blockDim.z * L * (C + (DC ? 1 : 0)) + (size_t)gl * L;
+    // COLS_STAT_EMBED: ONE such slot holds the DC rows while the tile is F (classification, the reads of the listed bins) and the inverse
+    // step's output twiddles exp(-2*pi*i*k*g/PH) from there to the tile's stores.  Both depend on (k, g) only, a group has exactly L threads
+    // (T*C = L from L = 16 on; the mode exists from L = 32), so thread (t, c) fetches entry k = t*C + c of the table that comes next (8 bytes out of L2, asked for a
+    // phase ahead) and writes it into the slot where the phase changes.  (A slot of its own for the twiddles is 2 KiB at L = 256: 42 KiB
+    // per workgroup, one workgroup per CU fewer than COLS_STAT; the entries kept in registers across the classification spilled there.)
+    float2* lds_wo = FUSED ? lds_ah : reinterpret_cast<float2*>(tfft_smem) + (size_t)blockDim.z * L * (C + (DC ? 1 : 0)) + (size_t)gl * L;
+    // (opaque: inside the tile loop these are loop-invariant loads, and hoisted they are the registers again)
+    auto fu_load_wo = [&]() -> float2 { return twload<-1>(tw, (int)((opaque_u32((unsigned)(t * C + c)) * (unsigned)g) & (unsigned)(P.PH - 1))); };
+    auto fu_load_ah = [&]() -> float2 { return P.dc_ah[(unsigned)P.out_a * opaque_u32((unsigned)(t * C + c)) + (unsigned)(P.out_b * g)]; };      // (FULL: every row exists)
+    if (FUSED && !DC) lds_wo[t * C + c] = fu_load_wo();      // (no DC rows: the slot never changes)
     if (DC) {
         for (int k = t * C + c; k < L; k += T * C) {       // forward: rows of the outputs; inverse: rows of the inputs
             const int row = (SIGN > 0) ? P.out_a * k + P.out_b * g : P.in_a * k + P.in_b * g;
@@ -1008,9 +1025,10 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
     constexpr int NOFF = 16;            // tiles per workgroup the offsets cover (the launcher caps tiles_per_block of the bucket modes)
     // inter-pass twiddles: registers (fetched once per workgroup) for short columns; from TFFT_COLS_LDS_TW_LOG on the L-entry table
     // exp(+2 pi i j/L) is staged in LDS and read at the point of use (at L = 512 they would be 46 more VGPRs in a kernel capped at 256)
-    constexpr bool TWL = (LOGL >= TFFT_COLS_LDS_TW_LOG);
+    // (COLS_STAT_EMBED: always the table -- the one exp(+2 pi i j/L) serves both directions, registers would hold one sign's)
+    constexpr bool TWL = (LOGL >= TFFT_COLS_LDS_TW_LOG) || FUSED;
     float2 W[TWL ? 1 : tw_regs<L, E>()];
-    float2* lds_tw = reinterpret_cast<float2*>(tfft_smem) + (size_t)blockDim.z * L * (C + (DC ? 1 : 0) + (TW ? 1 : 0));
+    float2* lds_tw = reinterpret_cast<float2*>(tfft_smem) + (size_t)blockDim.z * L * (C + (DC || FUSED ? 1 : 0) + (TW ? 1 : 0));
     float2* lds_aw = lds_tw + (TWL ? L : 0) + gl * C;      // COLS_READ with DC: the current tile's 16 column factors
     if (TWL) {
         const int tws = P.PH >> LOGL;
@@ -1048,7 +1066,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
     // the bucket offsets of the workgroup's tiles (at most NOFF: the launcher sees to it) sit in LDS: read with lgkmcnt, not vmcnt,
     // and without the branch trees a register array indexed by the tile turned into
     unsigned* lds_eo = reinterpret_cast<unsigned*>(lds_tw + (TWL ? L : 0) + blockDim.z * C) + gl * (NOFF + 2);
-    if (MODE == COLS_READ || embed_mode(MODE) || MODE == COLS_EMIT || MODE == COLS_STAT) {
+    if (MODE == COLS_READ || embed_mode(MODE) || MODE == COLS_EMIT || STAT) {
         const unsigned b0 = (unsigned)(((PI ? (int)blockIdx.z : plane) * P.G + (g < P.G ? g : 0)) * ntiles);      // (PI: blockIdx.z = 3*img + plane)
         for (int i = em_tid; i <= NOFF; i += em_nthr) lds_eo[i] = P.rd_off[b0 + (unsigned)imin(tile0 + i, ntiles)];
     }
@@ -1070,7 +1088,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
     };
     const float2* em_fl = P.em_fl + (size_t)img * P.em_n;
     const uint8_t* em_pb = P.em_pb + (size_t)img * P.em_n;
-    auto em_entries = [&](int tile, EmEntry (&en)[NE], bool with_value) {
+    auto em_entries = [&](int tile, EmEntry (&en)[NE], bool with_value, bool with_bit) {      // (COLS_STAT_EMBED: the bit alone, F comes out of the tile)
         unsigned e0, e1;
         em_range(tile, e0, e1);
 #pragma unroll
@@ -1079,7 +1097,8 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
             en[i].live = e < e1 ? 1u : 0u;
             const unsigned ec = en[i].live ? e : 0u;
             en[i].tb = P.rd_bins[ec];
-            if (with_value) { en[i].f = em_fl[ec]; en[i].bit = em_pb[ec]; }
+            if (with_value) en[i].f = em_fl[ec];
+            if (with_bit) en[i].bit = em_pb[ec];
         }
     };
     // adaptive alpha (S:704-710): this image's median of the plane (workgroup uniform)
@@ -1088,7 +1107,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
         if (MODE == COLS_EMBED_D) return f;       // (em_fl holds the delta itself)
         const float mag = fmaxf(1e-12f, mag_of(f));
         float ca = P.em_cos, sa = P.em_sin;
-        if (PH && P.em_med) sincosf(P.em_alpha * fminf(2.f, fmaxf(0.5f, mag / em_medp)), &sa, &ca);
+        if (MODE == COLS_EMBED && PH && P.em_med) sincosf(P.em_alpha * fminf(2.f, fmaxf(0.5f, mag / em_medp)), &sa, &ca);
         float2 nv = make_float2(mag * ca, bit ? mag * sa : -mag * sa);
         if (PH && P.em_jp) nv = cmul(nv, P.em_jp[e]);     // polar(mag, +-a + jitter[bit]): the phase of +-a turned by the bin's jitter
         if (conj) nv = cconj(nv);
@@ -1098,13 +1117,13 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
     // (128 slots behind the bucket offsets; flushed with one global atomic once more than 64 are waiting: a value adds at most 64)
     const int st_lin = (gl * T + t) * C + c, st_wave = st_lin >> 6;
     unsigned* st_wbuf = lds_eo + (blockDim.z - gl) * (NOFF + 2) + st_wave * TFFT_STAT_SLOTS;
-    SelectState* st_s = (MODE == COLS_STAT) ? P.st_sel + 3 * img + plane : nullptr;
-    const unsigned st_lo = (MODE == COLS_STAT) ? st_s->lo : 0u, st_span = (MODE == COLS_STAT) ? st_s->hi - st_lo : 0u, st_base = st_lo << 19;
+    SelectState* st_s = STAT ? P.st_sel + 3 * img + plane : nullptr;
+    const unsigned st_lo = STAT ? st_s->lo : 0u, st_span = STAT ? st_s->hi - st_lo : 0u, st_base = st_lo << 19;
     // (thresholds clamped at 0 -- mag2_threshold answers -inf for "everything passes", |F|^2 is never negative -- so that -1 can stand for
     // "not a bin of the annulus" in the comparisons below)
-    const float st_t2lo = (MODE == COLS_STAT) ? fmaxf(st_s->t2_lo, 0.f) : 0.f, st_t2hi = (MODE == COLS_STAT) ? fmaxf(st_s->t2_hi, 0.f) : 0.f;
-    unsigned* st_out = (MODE == COLS_STAT) ? P.st_cand + ((size_t)img * 3 + plane) * P.st_cand_stride : nullptr;
-    float* st_ambo = (MODE == COLS_STAT) ? P.st_amb + ((size_t)img * 3 + plane) * TFFT_AMB_CAP : nullptr;
+    const float st_t2lo = STAT ? fmaxf(st_s->t2_lo, 0.f) : 0.f, st_t2hi = STAT ? fmaxf(st_s->t2_hi, 0.f) : 0.f;
+    unsigned* st_out = STAT ? P.st_cand + ((size_t)img * 3 + plane) * P.st_cand_stride : nullptr;
+    float* st_ambo = STAT ? P.st_amb + ((size_t)img * 3 + plane) * TFFT_AMB_CAP : nullptr;
     // per-lane counters (one LDS atomic each at the end).  The classification is written for the VECTOR unit: a compare + add-with-carry
     // per counter and two branches on VCC per value.  Its first form counted with ballots and scalar popcounts: 39 scalar
     // instructions per value, and the scalar unit is shared by the CU's four SIMDs -- 0.21 ms of a 1080p batch's 0.66 (round 3).
@@ -1112,7 +1131,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
     // bucket in [lo, hi] <=> bits - st_base <= st_span_b; never beyond +inf, so that a negative value (column 0's stand-in) stays outside
     const unsigned st_span_raw = st_span >= 8192u ? 0xFFFFFFFFu : ((st_span << 19) | 0x7FFFFu);
     const unsigned st_span_b = st_base > 0x7F800000u ? 0u : (st_span_raw < 0x7F800000u - st_base ? st_span_raw : 0x7F800000u - st_base);
-    const unsigned st_aspan = (MODE == COLS_STAT && P.st_shi >= P.st_slo) ? P.st_shi - P.st_slo : 0u;       // annulus: d1 - s_lo <= st_aspan
+    const unsigned st_aspan = (STAT && P.st_shi >= P.st_slo) ? P.st_shi - P.st_slo : 0u;       // annulus: d1 - s_lo <= st_aspan
     const unsigned st_t2lo_b = __float_as_uint(st_t2lo), st_t2win = __float_as_uint(st_t2hi) - st_t2lo_b;  // threshold window on the bits (values >= 0)
     // Every wave of the launch owns P.st_resv slots at the head of the plane's candidate list (wave w of workgroup b: slots
     // (b * nwaves + w) * st_resv ..), fills what it does not use with TFFT_CAND_HOLE at the end (the select kernels skip those), and only a
@@ -1120,7 +1139,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
     // flush, whose round trip the wave sat out -- ~0.1 ms of a 1080p batch's 0.68; reserving with one atomic per wave at the start was
     // worse still, 0.99: a thousand waves per plane queue on one address at once.)
     unsigned* st_region = st_out + (size_t)(((blockIdx.y * gridDim.x + blockIdx.x) * ((blockDim.x * blockDim.y * blockDim.z + 63) >> 6)) + st_wave) * P.st_resv;
-    if (MODE == COLS_STAT && blockIdx.x == 0 && blockIdx.y == 0 && st_lin == 0) st_s->cand_fixed = P.st_cand_fixed;
+    if (STAT && blockIdx.x == 0 && blockIdx.y == 0 && st_lin == 0) st_s->cand_fixed = P.st_cand_fixed;
     unsigned st_used = 0;
     auto st_fill = [&]() {              // wave uniform
         for (unsigned i = st_used + (st_lin & 63); i < P.st_resv; i += 64) st_region[i] = TFFT_CAND_HOLE;
@@ -1142,24 +1161,24 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
         WaveSync::sync();
         st_nstaged = 0;
     };
-    if (embed_mode(MODE)) em_entries(tile0, enC, true);
-    if (PF && (MODE == COLS_EMIT || MODE == COLS_STAT || MODE == COLS_READ)) em_entries(tile0, enC, false);
+    if (embed_mode(MODE)) em_entries(tile0, enC, true, true);
+    if (PF && (MODE == COLS_EMIT || STAT || MODE == COLS_READ)) em_entries(tile0, enC, false, FUSED);
     for (int tile = tile0; tile < tile1; tile++) {
         if (!PF && !embed_mode(MODE)) {      // no prefetch: this tile's loads and list entries now; another resident workgroup covers the wait
             if (!has_bins(tile)) continue;
             load_tile(tile, u); awc = load_aw(tile);
-            if (MODE == COLS_EMIT || MODE == COLS_READ) em_entries(tile, enC, false);      // (COLS_STAT: after its classification, the registers are needed there)
+            if (MODE == COLS_EMIT || MODE == COLS_READ) em_entries(tile, enC, false, false);      // (COLS_STAT: after its classification, the registers are needed there)
         }
         // the next tile's loads ALWAYS go out (a load inside a branch cannot be counted by s_waitcnt: every later wait would drain the
         // queue): past the last tile, or when the next tile has no bins to read, this tile is fetched again (cache resident, never used)
         if (PF) { const int nt = (tile + 1 < tile1 && has_bins(tile + 1)) ? tile + 1 : tile; load_tile(nt, un); awn = load_aw(nt); }
-        if (PF && (MODE == COLS_EMIT || MODE == COLS_STAT || MODE == COLS_READ)) em_entries(tile + 1, enN, false);          // travels with the next tile's loads
+        if (PF && (MODE == COLS_EMIT || STAT || MODE == COLS_READ)) em_entries(tile + 1, enN, false, FUSED);          // travels with the next tile's loads
         if (embed_mode(MODE)) {
             // the tile of F' - F: zeros but for the bins of the list (S:712-732 per bin); a tile without bins is stored as zeros.
             // The values of tile+1's bins and the entries of tile+2 are fetched now (see em_* above the loop).
             bool hb = true;
             if (blockDim.z == 1) { unsigned e0, e1; em_range(tile, e0, e1); hb = e1 > e0; }      // workgroup-uniform: the barriers stay aligned
-            em_entries(tile + 1, enN, true);
+            em_entries(tile + 1, enN, true, true);
             if (hb) {
 #pragma unroll
                 for (int m = 0; m < E; m++) lds[lay.idx(t + m * T, c)] = make_float2(0.f, 0.f);
@@ -1228,7 +1247,10 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
 #pragma unroll
             for (int m = 0; m < E; m++) u[m] = csub(u[m], cmul(lds_ah[t + m * T], awc));
         }
-        if (TWL) fft_block_lazy<L, E, SIGN>(u, lds, lay, t, c, lds_tw, 1);
+        // (COLS_STAT_EMBED: the thread's row made opaque per transform -- the twiddle addresses that follow from it are loop invariant, and
+        // hoisted for two transforms they are 15 registers the classification between them has no room for)
+        if (FUSED) fft_block_lazy<L, E, SIGN>(u, lds, lay, (int)opaque_u32((unsigned)t), c, lds_tw, 1);
+        else if (TWL) fft_block_lazy<L, E, SIGN>(u, lds, lay, t, c, lds_tw, 1);
         else fft_block<L, E, SIGN>(u, lds, lay, t, c, W);
         if (MODE == COLS_READ) {
             // park the tile (row k of group g = spectrum row g + G*k) and read the bits of its bins in place
@@ -1307,7 +1329,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
             st_capcount += !(x < st_t2hi) ? 1u : 0u;
             st_ambflag = st_ambflag + st_ambflag + ((__float_as_uint(x) - st_t2lo_b < st_t2win) ? 1u : 0u);
         };
-        if (FULL && MODE == COLS_STAT && !ST_LDS) {
+        if (FULL && STAT && !ST_LDS) {
             // the DC row factors of TFFT_STAT_GROUP values are read together, ahead of those values' staging writes: the compiler cannot
             // tell the two LDS regions apart, so a read issued per value waited behind the previous value's write and out its own latency
 #ifndef TFFT_STAT_GROUP
@@ -1334,7 +1356,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
                 float2 v = u[m];
                 if (TW) v = cmul(v, lds_wo[t + m * T]);
                 if (DC && SIGN > 0) v = cadd(v, cmul(lds_ah[t + m * T], awc));      // last forward step: the rank-1 term comes back
-                if (MODE == COLS_STAT) {        // nothing is stored (L = 512: the values are classified from the parked tile below; shorter columns: above)
+                if (STAT) {        // nothing is stored (L = 512: the values are classified from the parked tile below; shorter columns: above)
                 } else if (MODE == COLS_EMIT && P.em_m2) {      // nothing but the statistics will read this: |F|^2, half the bytes (2: no statistics
                     if (P.em_m2 == 1) *reinterpret_cast<float*>(mb + m * (stride_out >> 1) + (vo >> 1)) = fmaf(v.x, v.x, v.y * v.y);      // asked for, nothing at all)
                 } else if (MODE == COLS_PLAIN && SIGN > 0 && hist_on) {      // the statistics' sample: a histogram instead of the narrow spectrum
@@ -1359,7 +1381,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
                 }
             }
         }
-        if (((MODE == COLS_EMIT && P.em_m2 == 1) || MODE == COLS_STAT) && tile == 0 && c == 0 && g < P.G) {      // the packed column 0 (its two real spectra cannot be told
+        if (((MODE == COLS_EMIT && P.em_m2 == 1) || STAT) && tile == 0 && c == 0 && g < P.G) {      // the packed column 0 (its two real spectra cannot be told
             float2* col0 = P.st_col0 + ((size_t)img * 3 + plane) * P.PH;                  // apart from magnitudes) travels beside the |F|^2 plane
             const int to = (int)opaque_u32((unsigned)t);
 #pragma unroll
@@ -1368,7 +1390,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
                 if (row < out_rows) col0[(unsigned)row] = (DC && SIGN > 0) ? cadd(u[m], cmul(lds_ah[to + m * T], awc)) : u[m];
             }
         }
-        if (MODE == COLS_EMIT || MODE == COLS_STAT) {
+        if (MODE == COLS_EMIT || STAT) {
             // park the tile (as COLS_READ does) and write the values of the listed bins, DC term included, into the list the first
             // inverse step embeds from: em_fl[entry index], coalesced
             lds_barrier();            // the last gather of fft_block has been consumed by every thread
@@ -1376,7 +1398,9 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
             for (int m = 0; m < E; m++) lds[lay.idx(t + m * T, c)] = u[m];
             if (DC && t == 0) lds_aw[c] = awc;
             lds_barrier();
-            if (MODE == COLS_STAT) {
+            float2 fu_wo = make_float2(0.f, 0.f);
+            if (FUSED && DC) fu_wo = fu_load_wo();      // needed once the tile's values have been read: the statistics' tail rides in between
+            if (STAT) {
                 if (ST_LDS) {
                     // L = 512: 32 values per thread -- classified in registers beside the transform's own 64 the kernel spills; from the
                     // parked tile instead, four values in flight
@@ -1435,27 +1459,85 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
                     }
                 }
             }
-            if (!PF && MODE == COLS_STAT) em_entries(tile, enC, false);
-            {
+            if (!PF && STAT) em_entries(tile, enC, false, FUSED);
+            // the value of a listed bin out of the parked tile, DC term included: what COLS_EMIT / COLS_STAT write to em_fl and COLS_STAT_EMBED embeds from
+            auto read_listed = [&](const TileBin tb) -> float2 {
+                float2 v = lds[lay.idx(tb.k, tb.c)];
+                if (DC) v = cadd(v, cmul(lds_ah[tb.k], lds_aw[tb.c]));
+                return v;
+            };
+            if constexpr (FUSED) {
+                // F at the tile's listed bins out of the parked tile into registers; then the tile becomes F' - F (zeros but for those bins)
+                // and goes back: COLS_EMBED's tile, built without the round trip of the values through P.em_fl.  A bucket with more than
+                // NE entries per thread parks the values of the rest in P.em_fl after all: each by the thread that reads it back below
+                unsigned e0, e1;
+                em_range(tile, e0, e1);
+                bool hb = true;
+                if (blockDim.z == 1) hb = e1 > e0;      // workgroup-uniform: the barriers stay aligned
+                if (hb) {
+                    float2* fl = P.em_fl + (size_t)img * P.em_n;
+#pragma unroll
+                    for (int i = 0; i < NE; i++) {
+                        const TileBin tb = enC[i].tb;
+                        enC[i].f = read_listed(tb);
+                    }
+                    for (unsigned e = e0 + (unsigned)(em_tid + NE * em_nthr); e < e1; e += em_nthr) {
+                        const TileBin tb = P.rd_bins[e];
+                        fl[e] = read_listed(tb);
+                    }
+                    lds_barrier();            // every read of the parked tile and of the DC rows is done
+#pragma unroll
+                    for (int m = 0; m < E; m++) lds[lay.idx(t + m * T, c)] = make_float2(0.f, 0.f);
+                    if (DC) lds_wo[t * C + c] = fu_wo;
+                    lds_barrier();
+#pragma unroll
+                    for (int i = 0; i < NE; i++)
+                        if (enC[i].live && enC[i].bit < 2u)
+                            lds[lay.idx(enC[i].tb.k, enC[i].tb.c)] = em_delta(enC[i].f, enC[i].bit, enC[i].tb.conj, e0 + (unsigned)(em_tid + i * em_nthr));
+                    for (unsigned e = e0 + (unsigned)(em_tid + NE * em_nthr); e < e1; e += em_nthr) {
+                        const TileBin tb = P.rd_bins[e];
+                        const unsigned bit = em_pb[e];
+                        if (bit >= 2u) continue;
+                        lds[lay.idx(tb.k, tb.c)] = em_delta(em_fl[e], bit, tb.conj, e);
+                    }
+                    lds_barrier();
+#pragma unroll
+                    for (int m = 0; m < E; m++) u[m] = lds[lay.idx(t + m * T, c)];
+                    lds_barrier();            // before the first exchange of the transform overwrites the tile
+                    fft_block_lazy<L, E, -1>(u, lds, lay, (int)opaque_u32((unsigned)t), c, lds_tw, 1);
+                }
+                // the inverse step's output rows k + L*g are this step's input rows: the same offsets, in `out`
+                char* ob = out_bytes + (size_t)tile * (C * sizeof(float2));
+                const unsigned vo = opaque_u32(voff_in);
+                float2 fu_ah = make_float2(0.f, 0.f);
+                if (DC) fu_ah = fu_load_ah();
+#pragma unroll
+                for (int m = 0; m < E; m++) {
+                    float2 v = make_float2(0.f, 0.f);
+                    if (hb) v = cmul(u[m], lds_wo[t + m * T]);
+                    *reinterpret_cast<float2*>(ob + m * stride_in + vo) = v;
+                }
+                static_assert(!FUSED || LOGL >= TFFT_TILE_FUSE_MIN_LOG, "COLS_STAT_EMBED: from L = 32 on");
+                if (DC && hb) {             // the slot goes back to the DC rows; the next tile's transform has a barrier before it reads them
+                    lds_barrier();          // (L >= 32: a transform with an exchange)
+                    lds_ah[t * C + c] = fu_ah;
+                } else if (!hb) lds_barrier();      // before the next tile's exchanges overwrite the parked values
+            } else {
                 unsigned e0, e1;
                 em_range(tile, e0, e1);
                 float2* fl = P.em_fl + (size_t)img * P.em_n;
 #pragma unroll
                 for (int i = 0; i < NE; i++) {      // no predicate on the store (see FULL): lanes without an entry write to the context's scratch line
                     const TileBin tb = enC[i].tb;
-                    float2 v = lds[lay.idx(tb.k, tb.c)];
-                    if (DC) v = cadd(v, cmul(lds_ah[tb.k], lds_aw[tb.c]));
                     float2* dst = enC[i].live ? fl + (e0 + (unsigned)(em_tid + i * em_nthr)) : reinterpret_cast<float2*>(P.trash) + em_tid;
-                    *dst = v;
+                    *dst = read_listed(tb);
                 }
                 for (unsigned e = e0 + (unsigned)(em_tid + NE * em_nthr); e < e1; e += em_nthr) {
                     const TileBin tb = P.rd_bins[e];
-                    float2 v = lds[lay.idx(tb.k, tb.c)];
-                    if (DC) v = cadd(v, cmul(lds_ah[tb.k], lds_aw[tb.c]));
-                    fl[e] = v;
+                    fl[e] = read_listed(tb);
                 }
+                lds_barrier();            // before the next tile's exchanges overwrite the parked values
             }
-            lds_barrier();            // before the next tile's exchanges overwrite the parked values
             if (PF) {
 #pragma unroll
                 for (int i = 0; i < NE; i++) enC[i] = enN[i];
@@ -1475,7 +1557,7 @@ __global__ void __launch_bounds__(cols_threads(LOGL)) TFFT_WAVES_PER_EU((MODE ==
                 if (lds_hist[i]) atomicAdd(&gh[i], lds_hist[i]);
         }
     }
-    if (MODE == COLS_STAT) {            // the workgroup's sums: one global atomic each (a per-thread atomic on one address per plane serialises)
+    if (STAT) {            // the workgroup's sums: one global atomic each (a per-thread atomic on one address per plane serialises)
         // (opaque: computed here, not carried through the tile loop in a register the allocator then spills)
         unsigned* st_wcnt = lds_eo + (blockDim.z - opaque_u32(threadIdx.z)) * (NOFF + 2) + ((blockDim.x * blockDim.y * blockDim.z + 63) >> 6) * TFFT_STAT_SLOTS;      // [0], [1]: the workgroup's sums
         st_fill();
@@ -2280,21 +2362,21 @@ static hipError_t launch_cols_t(const float2* in, float2* out, const float2* tw,
     int gpb = 256 / (T * C);
     if (gpb < 1) gpb = 1;
     if (gpb > Geff) gpb = Geff;
-    if constexpr (!FULL && (LOGL >= 6 || MODE == COLS_STAT || (MODE == COLS_PLAIN && SIGN > 0 && !TW)) && MODE != COLS_ROWLIMIT) {
+    if constexpr (!FULL && (LOGL >= 6 || stat_mode(MODE) || (MODE == COLS_PLAIN && SIGN > 0 && !TW)) && MODE != COLS_ROWLIMIT) {
         // every output element exists: the variant whose stores carry no predicate (ROWLIMIT cuts rows by definition; short columns
         // only for the statistics, whose classification / histogram live in that store loop)
         const int rows_out_max = P.out_a * (L - 1) + P.out_b * (P.G - 1);
-        if ((LOGL >= 6 || MODE == COLS_STAT || P.hist_sel) && rows_out_max < P.out_rows && P.M % C == 0 && Geff % gpb == 0)
+        if ((LOGL >= 6 || stat_mode(MODE) || P.hist_sel) && rows_out_max < P.out_rows && P.M % C == 0 && Geff % gpb == 0)
             return launch_cols_t<LOGL, SIGN, MODE, DC, TW, true, PH, PI>(in, out, tw, P, n_planes, s);
-        if (MODE == COLS_STAT) return hipErrorInvalidValue;      // the in-register classification lives in the unpredicated store loop only
+        if (stat_mode(MODE)) return hipErrorInvalidValue;      // the in-register classification lives in the unpredicated store loop only
     }
-    const size_t lds0 = (size_t)gpb * L * C * sizeof(float2) + (DC ? (size_t)gpb * L * sizeof(float2) : 0) + (TW ? (size_t)gpb * L * sizeof(float2) : 0) +
-                       (LOGL >= TFFT_COLS_LDS_TW_LOG ? (size_t)L * sizeof(float2) : 0);
+    const size_t lds0 = (size_t)gpb * L * C * sizeof(float2) + (DC || MODE == COLS_STAT_EMBED ? (size_t)gpb * L * sizeof(float2) : 0) + (TW ? (size_t)gpb * L * sizeof(float2) : 0) +
+                       (LOGL >= TFFT_COLS_LDS_TW_LOG || MODE == COLS_STAT_EMBED ? (size_t)L * sizeof(float2) : 0);      // (COLS_STAT_EMBED: see the kernel's lds_wo, TWL)
     int ntiles = (P.M + C - 1) / C;
     if (MODE == COLS_PLAIN && SIGN > 0 && P.tile_step > 1) ntiles = (ntiles - P.tile_off + P.tile_step - 1) / P.tile_step;      // the statistics' sample: every tile_step-th tile
     int tpb = P.tiles_per_block > 0 ? P.tiles_per_block : 1;
     ColParams Q = P;
-    constexpr bool BUCKETS = (MODE == COLS_READ || embed_mode(MODE) || MODE == COLS_EMIT || MODE == COLS_STAT);
+    constexpr bool BUCKETS = (MODE == COLS_READ || embed_mode(MODE) || MODE == COLS_EMIT || stat_mode(MODE));
     if (BUCKETS) {          // the bucket offsets of a workgroup's tiles are staged in LDS: 16 tiles + sentinel per group
         if (tpb > 16) tpb = 16;
         if (tpb > ntiles) tpb = ntiles;      // a grid narrower than the request: COLS_STAT's reservations (st_resv) go with the tiles a workgroup really has
@@ -2302,7 +2384,7 @@ static hipError_t launch_cols_t(const float2* in, float2* out, const float2* tw,
     }
     const size_t nwaves = ((size_t)C * T * gpb + 63) / 64;
     const size_t lds = lds0 + (BUCKETS ? (size_t)gpb * (C * sizeof(float2) + 18 * sizeof(unsigned)) : 0) +
-                       (MODE == COLS_STAT ? (nwaves * (TFFT_STAT_SLOTS + 1) + 2) * sizeof(unsigned) : 0);
+                       (stat_mode(MODE) ? (nwaves * (TFFT_STAT_SLOTS + 1) + 2) * sizeof(unsigned) : 0);
     size_t lds_total = lds;
     if (MODE == COLS_PLAIN && SIGN > 0 && P.hist_sel) {
         if (!FULL) return hipErrorInvalidValue;      // the histogram lives in the unpredicated store loop only
@@ -2311,19 +2393,22 @@ static hipError_t launch_cols_t(const float2* in, float2* out, const float2* tw,
     }
     if (gsample && (!FULL || P.g_off + (Geff - 1) * P.g_step >= P.G)) return hipErrorInvalidValue;
     dim3 grid((ntiles + tpb - 1) / tpb, (Geff + gpb - 1) / gpb, n_planes), block(C, T, gpb);      // n_planes = 3 * n_images
-    if (MODE == COLS_STAT) {
+    if (stat_mode(MODE)) {
         Q.st_resv = 64u * (unsigned)tpb;        // a wave stages ~45 of a tile's 1024 values (three sixteenth-octave buckets around the median)
         const size_t fixed = (size_t)grid.x * grid.y * nwaves * Q.st_resv;
         if (fixed + (size_t)P.PH * (P.M + 1) > P.st_cand_stride) return hipErrorInvalidValue;
         Q.st_cand_fixed = (unsigned)fixed;
     }
-    auto k = k_fft_cols<LOGL, SIGN, MODE, DC, TW, FULL, PH, PI>;
-    if (lds_total > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_total);
-        if (e != hipSuccess) return e;
+    if constexpr (MODE == COLS_STAT_EMBED && !FULL) return hipErrorInvalidValue;      // (never reached: the predicated form is not even built)
+    else {
+        auto k = k_fft_cols<LOGL, SIGN, MODE, DC, TW, FULL, PH, PI>;
+        if (lds_total > 48 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_total);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(k, grid, block, lds_total, s, in, out, tw, Q);
+        return hipGetLastError();
     }
-    hipLaunchKernelGGL(k, grid, block, lds_total, s, in, out, tw, Q);
-    return hipGetLastError();
 }
 // Which instantiations of k_fft_cols exist (FULL aside, which launch_cols_t picks): the guard of the dispatch below, so also what
 // launch_cols accepts.  The inverse knows the plain step and the first step of a delta embed (no DC term: the tile holds F' - F);
@@ -2336,11 +2421,12 @@ constexpr bool cols_variant_exists(int mode, int sign, bool dc, bool tw, bool ph
         case COLS_ROWLIMIT: return !tw && !ph && !pi;
         case COLS_READ: return !tw;
         case COLS_EMIT: case COLS_STAT: return !tw && !ph;
+        case COLS_STAT_EMBED: return !tw;      // (jitter: PH, as COLS_EMBED; the output twiddles are the inverse half's own, always on)
         default: return false;
     }
 }
 // a run-time value lo <= v <= hi as a compile-time one: f(std::integral_constant<int, v>).  launch_cols nests four of these, so the
-// innermost body exists 10 x 2 x 7 x 16 times on the host; where cols_variant_exists says no, that body is `return hipErrorInvalidValue`
+// innermost body exists 10 x 2 x 8 x 16 times on the host; where cols_variant_exists says no, that body is `return hipErrorInvalidValue`
 // alone and names no kernel, so only the existing forms are instantiated.  (The row launchers' sizes go through TFFT_DISPATCH_LOG.)
 template <int LO, int HI, class F>
 static hipError_t with_constant(int v, const F& f) {
@@ -2349,13 +2435,14 @@ static hipError_t with_constant(int v, const F& f) {
 }
 hipError_t launch_cols(const float2* in, float2* out, const float2* tw_ph, const ColParams& P, const ColStep& step, int n_planes, hipStream_t s) {
     const int mode = step.mode;
-    const bool fwd = step.sign > 0, emit = mode == COLS_EMIT || mode == COLS_STAT, buckets = emit || embed_mode(mode) || mode == COLS_READ;
+    const bool fwd = step.sign > 0, emit = mode == COLS_EMIT || stat_mode(mode), buckets = emit || embed_mode(mode) || mode == COLS_READ;
     if (step.logl > 9) return hipErrorInvalidValue;      // 512 x 16 x 8 B tiles: two workgroups per CU; plan_cols never asks for more
     // what the mode reads (the bucket modes redirect the stores of idle lanes to the context's scratch line)
     if (buckets && (!P.rd_bins || !P.trash)) return hipErrorInvalidValue;
     if ((emit || embed_mode(mode)) && !P.em_fl) return hipErrorInvalidValue;
     if (mode == COLS_ROWLIMIT && !P.last_row_dev) return hipErrorInvalidValue;
-    if (mode == COLS_STAT && (step.logl < 4 || !P.st_sel || !P.st_cand || !P.st_col0 || (P.st_cap && (!P.st_partial || !P.st_amb)))) return hipErrorInvalidValue;
+    if (mode == COLS_STAT_EMBED && (!fwd || !P.em_pb || P.em_m2 || in == out || P.in_a != 1 || P.in_b != (1 << step.logl) || P.out_b != 1)) return hipErrorInvalidValue;      // the last step of a two-step plan
+    if (stat_mode(mode) && (step.logl < 4 || !P.st_sel || !P.st_cand || !P.st_col0 || (P.st_cap && (!P.st_partial || !P.st_amb)))) return hipErrorInvalidValue;
     // fields that change what a launch does, in the one mode that honours them
     if (P.em_m2 && fwd && !(emit && P.st_col0)) return hipErrorInvalidValue;      // |F|^2 planes: COLS_EMIT (COLS_STAT stores nothing, the inverse step ignores it)
     if ((P.tile_step > 1 || P.gate) && !(mode == COLS_PLAIN && fwd && !P.tw_out)) return hipErrorInvalidValue;      // plain final forward step only
@@ -2364,11 +2451,11 @@ hipError_t launch_cols(const float2* in, float2* out, const float2* tw_ph, const
     const int sw = (P.dc_ah ? 1 : 0) | (P.tw_out ? 2 : 0) | (P.em_jp || P.em_med ? 4 : 0) | (step.walks ? 8 : 0);
     return with_constant<0, 9>(step.logl, [&](auto logl) {
         return with_constant<0, 1>(fwd ? 1 : 0, [&](auto f) {
-            return with_constant<COLS_PLAIN, COLS_EMBED_D>(mode, [&](auto m) {
+            return with_constant<COLS_PLAIN, COLS_STAT_EMBED>(mode, [&](auto m) {
                 return with_constant<0, 15>(sw, [&](auto w) {
                     constexpr int LOGL = decltype(logl)::value, SIGN = decltype(f)::value ? +1 : -1, MODE = decltype(m)::value, SW = decltype(w)::value;
                     constexpr bool DC = SW & 1, TW = SW & 2, PH = SW & 4, PI = SW & 8;
-                    if constexpr (cols_variant_exists(MODE, SIGN, DC, TW, PH, PI)) return launch_cols_t<LOGL, SIGN, MODE, DC, TW, false, PH, PI>(in, out, tw_ph, P, n_planes, s);
+                    if constexpr (cols_variant_exists(MODE, SIGN, DC, TW, PH, PI) && !(MODE == COLS_STAT_EMBED && LOGL < TFFT_TILE_FUSE_MIN_LOG)) return launch_cols_t<LOGL, SIGN, MODE, DC, TW, false, PH, PI>(in, out, tw_ph, P, n_planes, s);
                     else return hipErrorInvalidValue;
                 });
             });
